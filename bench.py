@@ -14,8 +14,8 @@ Protocol (VERDICT r1 "next round" 1-2):
     S (`--streams`, default 0 = automatic) is picked for the burst length K in an untimed calibration: a queue that
     went idle at the synchronize takes ~20 us to wake up, so short regions want fewer launches in flight than the
     steady state does (profiles/r02_region_overhead.txt); the calibration's numbers are in the line;
-  * the region is repeated (>= 5 times) and the MEDIAN region gives `value` / `ms_per_step`, so that a 20-step region
-    reports the same figure as a 200-step one;
+  * the timed steps are exactly `--steps` K: one region of K steps, whose wall time over K is `ms_per_step`
+    (`--regions R` repeats the region R times and takes the MEDIAN region, for profiling runs);
   * a fresh input batch every step (12 batches rotate: no step re-reads the previous step's frames out of the 256 MB
     Infinity Cache);
   * `roofline.kernel_ms` = GPU time per step from HIP events recorded on the launch streams around a long
@@ -35,6 +35,7 @@ import math
 import os
 import platform
 import statistics
+import subprocess
 import sys
 import threading
 import time
@@ -229,7 +230,7 @@ def verify_against_oracle(torch, pkg, plan, frames_t, W, H, cl, rm, aspect, n_ch
 
 
 def run_workload(torch, pkg, name, batch, steps, warmup, regions, dist=None, seed=1234, variant=-1, nsets=12,
-                 streams=4, kind="noise", aspect=False, serial_leg=True, verify=True, streams_auto=None):
+                 streams=4, kind="noise", aspect=False, serial_leg=True, verify=True, streams_auto=None, keep_last=False):
     sw, sh, W, H, cl, rm = WORKLOADS[name]
     assert nsets % streams == 0 and all(nsets % c == 0 for c in (streams_auto or ()))
     sets = [make_frames(torch, batch, sw, sh, seed + 7919 * s, kind) for s in range(nsets)]
@@ -277,6 +278,11 @@ def run_workload(torch, pkg, name, batch, steps, warmup, regions, dist=None, see
     run.issue(warmup)
     torch.cuda.synchronize()
     walls = [run.region(steps, dist) for _ in range(regions)]
+    last = None
+    if keep_last:  # the timed regions' last step k rendered plans[k % nsets] into lane k % streams (region() synchronised)
+        k = run.step - 1
+        last = {"slab": run.outs[k % streams].cpu().numpy(), "lens": run.lns[k % streams].cpu().numpy().astype("uint32"),
+                "stride": run.stride}
     gpu_ms = run.gpu_ms_per_step(max(200, steps))
     f0 = pkg.frame_setup(sets[0].data_ptr(), sw, sh, W, H, rm, aspect, aspect, False)
     cells_px = f0.out_w * f0.out_h  # sampled pixels per frame (2 rows per text row in half-block)
@@ -286,7 +292,7 @@ def run_workload(torch, pkg, name, batch, steps, warmup, regions, dist=None, see
                out_bytes_per_frame=out_mean / batch, alg_bytes_per_launch=alg_bytes, variant=plans[0].variant,
                input_sets=nsets, streams=streams, kind=kind, aspect=aspect, verify=ver, streams_autotune=tune,
                cells_per_frame=(f0.pad_left + f0.out_w) * ((f0.out_h + 1) // 2 if rm == 2 else f0.out_h),
-               serial=None, plans=plans, sets=sets, forced_variant=variant)
+               serial=None, plans=plans, sets=sets, forced_variant=variant, last=last)
     if serial_leg:
         # the same steps one launch at a time (each plan re-chooses its geometry for the whole GPU), and the same
         # batch rendered every step (its sampled lines then come out of the Infinity Cache)
@@ -396,13 +402,14 @@ def time_with_d2h(torch, plan, n, steps):
     return (time.perf_counter() - t0) / steps, int(buf.numel())
 
 
-def run_grid9(torch, pkg, steps, regions, targets=256, dist=None, world=1, rank=0, backend="nccl"):
+def run_grid9(torch, pkg, steps, regions, targets=256, dist=None, world=1, rank=0, backend="nccl", last=None):
     """BASELINE configs[3]: nine 1080p sources -> the 3x3 grid at 160x48 (stream.c:523-854), sharded over the ranks
     with an RCCL all-gather for the composite -- through the C-ABI (asciichat_hip_comm_* / asciichat_hip_grid_*):
     a step = every rank resizes the sources it owns into their tiles, ONE ncclAllGather moves the tiles to every rank,
     and every rank renders the grid for its `targets` target clients (the server renders the mixed frame once per
     connected client, render.c:340-600) straight from the gathered tiles -- the W x 2H canvas stays virtual.  The
-    exchange is inside the timed step.  World size 1 still runs the real ncclAllGather."""
+    exchange is inside the timed step.  World size 1 still runs the real ncclAllGather.  `last` (a dict): filled with
+    the output of the last timed step of the `targets` leg (the one the line reports)."""
     import numpy as np
 
     import orc
@@ -461,6 +468,8 @@ def run_grid9(torch, pkg, steps, regions, targets=256, dist=None, world=1, rank=
         for _ in range(5):
             step()
         walls = [region(steps) for _ in range(regions)]
+        if last is not None and label == f"{targets}_targets":
+            last.update(slab=slab.cpu().numpy(), lens=ln.cpu().numpy().astype("uint32"), stride=plan.stride)
         if dist is not None:
             t = torch.tensor(walls, dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -890,8 +899,9 @@ def maybe_spawn_ranks(args):
 
     import torch
 
-    have = torch.cuda.device_count()
-    if backend == "nccl" and have < args.gpus:
+    # (only RCCL needs the count: a gloo run's ranks share the visible GPUs, and this process then never opens one)
+    have = torch.cuda.device_count() if backend == "nccl" else args.gpus
+    if have < args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} needs {args.gpus} HIP devices, {have} visible (one process per GPU; "
                          "RCCL refuses two ranks on one device)")
     with socket.socket() as sk:
@@ -900,7 +910,8 @@ def maybe_spawn_ranks(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a fresh child, not exec: this process may have opened the HIP runtime (device_count above)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def rank_comm(torch, pkg, dist, world, rank, backend):
@@ -1112,12 +1123,40 @@ def emit_text(full, extra_path):
     return text
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20251015
+
+
+def dump_outputs(out_dir, last, prefix=""):
+    """--dump-outputs: what the timed path handed its caller in its last step, as .npy files in `out_dir`:
+    frame_lengths (every frame's byte count, float64), frame_index (the frames whose bytes follow, float64) and
+    frame_bytes (those frames' bytes one after another, float32).  All frames while they fit DUMP_MAX_BYTES at the
+    slab's stride, else a fixed, seeded sample of them: the same frames for the same arguments."""
+    import numpy as np
+
+    lens, slab, stride = last["lens"], last["slab"], last["stride"]
+    if (lens >= 0xFFFFFFF0).any():
+        raise SystemExit("bench.py: the dumped step reported overflow / bad descriptor")
+    n = len(lens)
+    fit = (DUMP_MAX_BYTES - 16 * n) // (4 * stride)
+    if fit < 1:
+        raise SystemExit(f"bench.py: --dump-outputs: one frame of stride {stride} exceeds {DUMP_MAX_BYTES} bytes as float32")
+    idx = np.arange(n) if fit >= n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, fit, replace=False))
+    data = [slab[i * stride:i * stride + int(lens[i])] for i in idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "frame_lengths.npy"), lens.astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "frame_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "frame_bytes.npy"), np.concatenate(data).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--regions", type=int, default=0, help="timed regions of --steps steps each; 0 = max(5, 1200 / steps)")
+    ap.add_argument("--regions", type=int, default=1,
+                    help="timed regions of --steps steps each (the median region gives value / ms_per_step); the default, "
+                         "1, times exactly --steps steps")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--workload", default="1080p_80x24_truecolor", choices=sorted(WORKLOADS) + ["grid9"],
                     help="grid9 = BASELINE configs[3]: nine 1080p sources -> 3x3 grid at 160x48, sharded over the ranks "
@@ -1141,6 +1180,8 @@ def main():
     ap.add_argument("--batch-sweep", default="256,1024,4096",
                     help="frames per launch for the batch-size axis of the headline, configs[2] and the sampled-image shapes "
                          "(N = 1, the default workload only); '' = none")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (frame lengths and bytes) as DIR/*.npy")
     ap.add_argument("--no-hot", action="store_true",
                     help="skip the one-launch-at-a-time / same-batch comparison legs (profiling runs)")
     args = ap.parse_args()
@@ -1159,7 +1200,9 @@ def main():
 
     if args.others in ("none", "''", '""'):
         args.others = ""
-    regions = args.regions if args.regions > 0 else max(5, min(60, 1200 // max(1, args.steps)))
+    if args.steps < 1 or args.regions < 1:
+        raise SystemExit("bench.py: --steps and --regions must be at least 1")
+    regions = args.regions
 
     import torch
 
@@ -1190,7 +1233,10 @@ def main():
     if world > 1 and backend == "nccl" and torch.cuda.device_count() < world:
         raise SystemExit(f"bench.py: {world} ranks but {torch.cuda.device_count()} HIP device(s) visible")
     if args.workload == "grid9":
-        g = run_grid9(torch, pkg, args.steps, regions, args.batch, dist, world, rank, backend)
+        last = {}
+        g = run_grid9(torch, pkg, args.steps, regions, args.batch, dist, world, rank, backend, last=last)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, f"rank{rank}_" if world > 1 else "")
         e = g[f"{args.batch}_targets"]
         if rank == 0:
             emit({
@@ -1212,7 +1258,10 @@ def main():
     res = run_workload(torch, pkg, args.workload, args.batch, args.steps, args.warmup, regions, dist, seed=1234 + rank,
                        variant=args.variant, nsets=args.input_sets, streams=args.streams or 4, kind=args.input,
                        aspect=args.aspect, serial_leg=not args.no_hot,
-                       streams_auto=(1, 2, 3, 4) if args.streams == 0 and world == 1 else None)
+                       streams_auto=(1, 2, 3, 4) if args.streams == 0 and world == 1 else None,
+                       keep_last=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res.pop("last"), f"rank{rank}_" if world > 1 else "")
     walls = res["walls"]
     per_rank_fps, multi = None, None
     if dist is not None:  # MAX over ranks of every region's wall time

@@ -1,6 +1,10 @@
 """One rank of tests/test_comm_two_ranks.py: drives ascii-chat_amd/csrc/comm.c with a world of `world` ranks.
 
-usage: comm_worker.py <rank> <world> <uid_file> <shared_gpu 0|1> [full]
+usage: comm_worker.py <rank>[,<rank>...] <world> <uid_file> <shared_gpu 0|1> [full]
+
+Several ranks in one process (a comma-separated list, shared_gpu 1 only) run as one thread each, so that a world larger
+than the number of processes a shared GPU may be opened by still runs on it; the environment that comm.c reads is changed
+only between two barriers of the process's ranks.
 
 "full" (the world-8 test): the batch is BASELINE's 256 frames (32 per rank at world 8), and frames of configs[4]'s size
 (4K -> 400x120 half blocks: 1.8 MB each) go through the packed gather too.
@@ -11,10 +15,11 @@ Every rank renders ITS block of a sharded batch, then checks after
   * asciichat_hip_grid_exchange             -- the 3x3 (and, with a client without video, 2x3) grid rendered from the
                                                gathered tiles against the oracle's composite + convert, for source counts
                                                that shard unevenly over the ranks (grid_slot_of).
-Prints "ok rank <r>" as its last line; any mismatch raises.
+Prints "ok rank <r>" for each of its ranks, in the order given, as its last lines; any mismatch raises.
 """
 import os
 import sys
+import threading
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,8 +27,62 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+class LocalRanks:
+    """The ranks this process hosts.  Process-wide state (the environment) changes only while all of them wait between two
+    barriers: a rank that passed the first has returned from its previous collective, which every rank of the world had
+    to enter, so nobody is still about to read the old value."""
+
+    def __init__(self, ranks):
+        self.ranks = ranks
+        self.barrier = threading.Barrier(len(ranks), timeout=300)
+
+    def set_env(self, rank, key, value):
+        self.barrier.wait()
+        if rank == self.ranks[0]:
+            if value is None:
+                os.environ.pop(key, None)
+            else:
+                os.environ[key] = value
+        self.barrier.wait()
+
+
 def main():
-    rank, world, uid_file, shared = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], int(sys.argv[4])
+    ranks = [int(r) for r in sys.argv[1].split(",")]
+    world, uid_file, shared = int(sys.argv[2]), sys.argv[3], int(sys.argv[4])
+    full = len(sys.argv) > 5 and sys.argv[5] == "full"
+    assert len(ranks) == 1 or shared, "several ranks in one process need the shared GPU"
+    import torch  # noqa: F401  (imported once, before the rank threads)
+
+    from __graft_entry__ import load_package
+
+    load_package().lib()
+    local = LocalRanks(ranks)
+    if len(ranks) == 1:
+        run_rank(ranks[0], world, uid_file, shared, full, local)
+    else:
+        errors = {}
+
+        def body(r):
+            try:
+                run_rank(r, world, uid_file, shared, full, local)
+            except BaseException as e:  # noqa: BLE001  (reported by the main thread)
+                import traceback
+
+                errors[r] = traceback.format_exc()
+                local.barrier.abort()
+
+        threads = [threading.Thread(target=body, args=(r,)) for r in ranks]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        if errors:
+            raise SystemExit("\n".join(f"rank {r}:\n{tb}" for r, tb in sorted(errors.items())))
+    for r in ranks:
+        print(f"ok rank {r}")
+
+
+def run_rank(rank, world, uid_file, shared, full, local):
     import numpy as np
     import torch
 
@@ -50,7 +109,6 @@ def main():
     L = pkg.lib()
     import ctypes as C
 
-    full = len(sys.argv) > 5 and sys.argv[5] == "full"
     # ---- (1) a batch of 7 frames sharded (4, 3): slots = 4, the last slot of rank 1 stays empty ------------------------
     # (full: 256 frames, 32 x 8 at world 8)
     n, W, H = (256 if full else 7), 40, 12
@@ -93,10 +151,7 @@ def main():
             assert ph[off[s]:off[s] + plen[s]].tobytes() == exp[f_r.value + i], f"rank {rank}: packed frame {f_r.value + i} differs"
     # ---- (2a) both forms behind the one entry: by argument and by the environment (what the first A/B on a real node runs)
     for form, env in ((0, None), (1, None), (-1, "slab"), (-1, "packed"), (-1, None)):
-        if env is None:
-            os.environ.pop("ASCIICHAT_HIP_GATHER", None)
-        else:
-            os.environ["ASCIICHAT_HIP_GATHER"] = env
+        local.set_env(rank, "ASCIICHAT_HIP_GATHER", env)
         slab3, ln3 = slab2.clone(), ln2.clone()
         packed3 = torch.zeros(world * slots * stride, dtype=torch.uint8, device="cuda")
         base, off3, len3, blk3, took = comm.all_gather_frames(slab3.data_ptr(), stride, ln3.data_ptr(), slots, packed3.data_ptr(),
@@ -113,7 +168,7 @@ def main():
                 s = r * slots + i
                 assert (len3 is None) == (took == 1) and (len3 is None or len3[s] == int(l3[s]))
                 assert wh[off3[s]:off3[s] + int(l3[s])].tobytes() == exp[f_r.value + i], f"rank {rank}: form {took} frame {f_r.value + i} differs"
-    os.environ.pop("ASCIICHAT_HIP_GATHER", None)
+    local.set_env(rank, "ASCIICHAT_HIP_GATHER", None)
     plan.close()
     # ---- (2b) frames of configs[4]'s size through the packed gather: 1.8 MB each, one per rank plus one (uneven shards), so
     # that a rank's block spans several of the transport's chunks and the lengths-first sizing sees megabytes
@@ -171,7 +226,6 @@ def main():
             plan.close()
         grid.close()
     comm.close()
-    print(f"ok rank {rank}")
 
 
 if __name__ == "__main__":

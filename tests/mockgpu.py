@@ -4,6 +4,8 @@ flat-combining layer), plans and the frame table, which otherwise need a GPU box
 has no such mode (it fails with ERR_NO_DEVICE without a GPU)."""
 import ctypes as C
 import os
+import platform
+import shutil
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,6 +18,15 @@ HOST_C = ["dropin.c", "combine.c", "plan.c", "achip_host.c", "hostutil.c", "buff
 HIP_INC = "/opt/rocm/include"
 
 
+def sanitized_argv(san, argv):
+    """The command line that runs a harness built with -fsanitize=`san`.  ThreadSanitizer's fixed shadow layout does not
+    cover every address a kernel with high-entropy address-space randomisation hands out ("FATAL: ThreadSanitizer:
+    unexpected memory mapping"), so its harnesses run with randomisation off for that one process (setarch -R)."""
+    if "thread" in san.split(",") and shutil.which("setarch"):
+        return ["setarch", platform.machine(), "-R"] + list(argv)
+    return list(argv)
+
+
 def _newer(target, deps):
     return os.path.exists(target) and all(os.path.getmtime(d) <= os.path.getmtime(target) for d in deps)
 
@@ -24,7 +35,7 @@ def _deps():
     d = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(INC, f) for f in os.listdir(INC)]
     d += [os.path.join(MOCK, f) for f in os.listdir(MOCK) if f.endswith((".c", ".cpp"))]
     d += [os.path.join(EMU, f) for f in os.listdir(EMU) if f.endswith((".cpp", ".h", ".hpp"))]
-    return d
+    return d + [os.path.abspath(__file__)]  # (the build recipes below)
 
 
 def build_library():
@@ -43,7 +54,9 @@ def build_library():
     lobj = os.path.join(BUILD, "mock_launch" + tag + ".o")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-DACHIP_ALL_GEOMETRIES", "-I" + EMU, "-I" + CSRC, "-I" + INC, "-c",
                            os.path.join(MOCK, "mock_launch.cpp"), "-o", lobj])
-    subprocess.check_call(["g++", "-shared", "-o", so + tag, *objs, lobj, "-lpthread", "-lm", "-ldl"])
+    # -Bsymbolic: the host C's hip* calls bind to the mock runtime inside this library even when a real libamdhip64 is in
+    # the process's global scope (librccl, which comm.c loads RTLD_GLOBAL, brings one in after a GPU test)
+    subprocess.check_call(["g++", "-shared", "-Wl,-Bsymbolic", "-o", so + tag, *objs, lobj, "-lpthread", "-lm", "-ldl"])
     os.replace(so + tag, so)
     for o in objs + [lobj]:
         os.remove(o)

@@ -33,11 +33,13 @@ def test_loopback_transport_builds_and_exports_what_comm_c_resolves():
         assert hasattr(so, name), name
 
 
-def run_world(world, env_extra, shared_gpu, tmp_path, full=False):
+def run_world(world, env_extra, shared_gpu, tmp_path, full=False, ranks_per_process=1):
     uid = str(tmp_path / "uid.bin")
     env = dict(os.environ, **env_extra)
-    procs = [subprocess.Popen([sys.executable, WORKER, str(r), str(world), uid, "1" if shared_gpu else "0"] + (["full"] if full else []), env=env,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
+    groups = [list(range(r, min(r + ranks_per_process, world))) for r in range(0, world, ranks_per_process)]
+    procs = [subprocess.Popen([sys.executable, WORKER, ",".join(map(str, g)), str(world), uid, "1" if shared_gpu else "0"] +
+                              (["full"] if full else []), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+             for g in groups]
     outs = []
     for p in procs:
         try:
@@ -47,8 +49,8 @@ def run_world(world, env_extra, shared_gpu, tmp_path, full=False):
                 q.kill()
             raise
         outs.append(out)
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0 and out.strip().splitlines()[-1] == f"ok rank {r}", f"rank {r}:\n{out[-3000:]}"
+    for g, p, out in zip(groups, procs, outs):
+        assert p.returncode == 0 and out.strip().splitlines()[-len(g):] == [f"ok rank {r}" for r in g], f"ranks {g}:\n{out[-3000:]}"
 
 
 @pytest.mark.gpu
@@ -59,10 +61,12 @@ def test_comm_world2_over_loopback_transport_on_one_gpu(tmp_path):
 @pytest.mark.gpu
 def test_comm_world8_over_loopback_transport_on_one_gpu(tmp_path):
     """The driver's 8-GPU run, de-risked without the hardware: comm.c at world 8 over the stand-in
-    transport, eight processes on the one GPU -- BASELINE's 256 frames sharded 32 x 8 through the slab and packed gathers,
-    frames of configs[4]'s size (1.8 MB) through the packed gather, configs[3]'s nine sources dealt (2, 1, 1, 1, 1, 1, 1, 1)
-    through grid_slot_of (and five / three sources: ranks that own nothing).  No scaling number follows from this."""
-    run_world(8, {"ASCIICHAT_HIP_RCCL_LIB": build_loopback()}, True, tmp_path, full=True)
+    transport on the one GPU, as four processes of two ranks each (a thread per rank: a shared GPU may not be opened by eight
+    processes at once; the transport's barriers work the same within a process as across processes) -- BASELINE's 256
+    frames sharded 32 x 8 through the slab and packed gathers, frames of configs[4]'s size (1.8 MB) through the packed
+    gather, configs[3]'s nine sources dealt (2, 1, 1, 1, 1, 1, 1, 1) through grid_slot_of (and five / three sources: ranks
+    that own nothing).  No scaling number follows from this."""
+    run_world(8, {"ASCIICHAT_HIP_RCCL_LIB": build_loopback()}, True, tmp_path, full=True, ranks_per_process=2)
 
 
 @pytest.mark.gpu

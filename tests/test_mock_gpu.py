@@ -536,7 +536,7 @@ def test_combiner_under_sanitizers(san):
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=0")
     for budget, nthreads in (("1000", "6"), ("2", "24"), ("2", "48")):
         env["ASCIICHAT_HIP_CPU_BUDGET"] = budget
-        p = subprocess.run([exe, nthreads, "300"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        p = subprocess.run(mockgpu.sanitized_argv(san, [exe, nthreads, "300"]), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert p.returncode == 0, (san, budget, p.stdout.decode()[-400:], p.stderr.decode()[-3000:])
         assert b"ok:" in p.stdout
 
@@ -549,6 +549,6 @@ def test_frame_table_locking_under_sanitizers(san):
     sanitizer; afterwards every slot renders to the line of a published image"""
     exe = mockgpu.build_thread_harness(san, "frame_table_threads_mock")
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=0")
-    p = subprocess.run([exe, "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    p = subprocess.run(mockgpu.sanitized_argv(san, [exe, "2"]), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, (san, p.stdout.decode()[-400:], p.stderr.decode()[-3000:])
     assert b"ok:" in p.stdout
