@@ -1,6 +1,7 @@
 /* achip_host.c -- see achip_host.h.  Plain C11, no GPU calls. */
 #include "achip_host.h"
 #include "internal.h"
+#include "render_variants.h"
 
 #include <math.h>
 #include <stdatomic.h>
@@ -506,10 +507,6 @@ bool achip_palette_ascii_only(const char *palette_chars) {
   return true;
 }
 
-/* the stream-kernel family (render_variants.h: ACHIP_STREAM_VARIANTS; render_stream.hpp: ACHIP_STREAM_MAXBLK) */
-#define ACHIP_HOST_STREAM_FIRST 16
-#define ACHIP_HOST_STREAM_MAXBLK 2048
-
 /* The kernels address a source with 32-bit byte offsets (a frame is at most tens of MB): a descriptor whose last pixel
  * lies 4 GiB or more behind its first -- only possible with an absurd explicit row stride -- is refused on the host. */
 bool achip_frame_extent_ok(const achip_frame_t *f) {
@@ -533,24 +530,27 @@ long achip_max_cells(const achip_frame_t *frames, int n_frames) {
   return max_cells;
 }
 
-/* the rows-kernel family (render_variants.h: ACHIP_ROWS_VARIANTS): a block is a whole number of text rows */
-#define ACHIP_HOST_ROWS_FIRST 24
-#ifndef ACHIP_ROWS_WIDE_CPL
-#define ACHIP_ROWS_WIDE_CPL 5 /* (render_variants.h) */
-#endif
-#ifndef ACHIP_ROWS_PARTS_CPL
-#define ACHIP_ROWS_PARTS_CPL 2 /* (render_variants.h) */
-#endif
-static int rows_variant_cpl(int variant) {
-  return variant == 24 || variant == 26 ? 7 : variant == 25 ? 4 : variant == 27 || variant == 29 ? ACHIP_ROWS_WIDE_CPL
-         : variant == 31 ? ACHIP_ROWS_PARTS_CPL : variant == 32 || variant == 28 ? 2 : variant == 30 || variant == 33 || variant == 34 ? 1 : 0;
+/* Facts of the stream and rows geometries, from their tables (render_variants.h: every id, built in this configuration or
+ * not); 0 for an id that is no geometry of the family */
+#define GEOMETRY_CPL(id, waves, cpl) case id: return cpl;
+#define GEOMETRY_WAVES(id, waves, cpl) case id: return waves;
+static int stream_cpl(int variant) {
+  switch (variant) { ACHIP_STREAM_TABLE(GEOMETRY_CPL, GEOMETRY_CPL, GEOMETRY_CPL) }
+  return 0;
 }
-/* the geometries that share a frame's blocks out over workgroups (render_variants.h ACHIP_ROWS_VARIANT_PARTS): fast sampler only */
-static bool rows_variant_parts(int variant) { return variant == 31 || variant == 32 || variant == 33 || variant == 34; }
-/* the geometries whose blocks are SEGMENTS of a row (render_variants.h ACHIP_ROWS_VARIANT_WIDE; render_rows.hpp WIDE): rows of
- * at most `waves` segments of 64 * cpl cells, and of at most ACHIP_ROWS_WIDE_MAX_ROW cells */
-#define ACHIP_HOST_ROWS_WIDE_MAX_ROW 4096
-static int rows_variant_wide_waves(int variant) { return variant == 27 ? 16 : variant == 29 ? 8 : variant == 30 || variant == 32 ? 4 : variant == 34 ? 2 : 0; }
+/* the rows-kernel family (ACHIP_ROWS_TABLE): a block is a whole number of text rows */
+static int rows_cpl(int variant) {
+  switch (variant) { ACHIP_ROWS_TABLE(GEOMETRY_CPL, GEOMETRY_CPL, GEOMETRY_CPL) }
+  return 0;
+}
+/* the geometries whose blocks are SEGMENTS of a row (ACHIP_ROWS_VARIANT_WIDE; render_rows.hpp WIDE): rows of at most `waves`
+ * segments of 64 * cpl cells, and of at most ACHIP_ROWS_WIDE_MAX_ROW cells; 0 for the others */
+static int rows_wide_waves(int variant) {
+  if (!ACHIP_ROWS_VARIANT_WIDE(variant))
+    return 0;
+  switch (variant) { ACHIP_ROWS_TABLE(GEOMETRY_WAVES, GEOMETRY_WAVES, GEOMETRY_WAVES) }
+  return 0;
+}
 /* segments of a padded row of wp cells (the kernel's own arithmetic: equal widths, the last one shorter, never empty) */
 static long rows_wide_segments(long wp, int cpl) {
   if (wp <= 0)
@@ -559,11 +559,11 @@ static long rows_wide_segments(long wp, int cpl) {
   return (wp + segw - 1) / segw;
 }
 /* the widest padded row a rows geometry takes */
-static int rows_variant_max_row(int variant) {
-  const int cpl = rows_variant_cpl(variant), waves = rows_variant_wide_waves(variant);
+static int rows_max_row(int variant) {
+  const int cpl = rows_cpl(variant), waves = rows_wide_waves(variant);
   if (!waves)
     return 64 * cpl;
-  return 64 * cpl * waves < ACHIP_HOST_ROWS_WIDE_MAX_ROW ? 64 * cpl * waves : ACHIP_HOST_ROWS_WIDE_MAX_ROW;
+  return 64 * cpl * waves < ACHIP_ROWS_WIDE_MAX_ROW ? 64 * cpl * waves : ACHIP_ROWS_WIDE_MAX_ROW;
 }
 
 /* ASCIICHAT_HIP_ROWS_PARTS (diagnostics, read once): 1 = the run-structured modes' small launches are never shared out over
@@ -585,6 +585,11 @@ static int rows_parts_forced(void) {
   static _Atomic int forced = -1;
   return env_int_once(&forced, "ASCIICHAT_HIP_ROWS_PARTS");
 }
+/* ASCIICHAT_HIP_STREAM_PARTS (diagnostics, read once): 1 = never, N = this many where the CUs allow */
+static int stream_parts_forced(void) {
+  static _Atomic int forced = -1;
+  return env_int_once(&forced, "ASCIICHAT_HIP_STREAM_PARTS");
+}
 static int rows_parts_wide_level(void) { /* 0: never; 1 (default): the modes it was measured ahead for; 2 (diagnostics): all five */
   static _Atomic int on = -1;
   int v = atomic_load_explicit(&on, memory_order_relaxed);
@@ -600,7 +605,7 @@ static int rows_parts_wide_level(void) { /* 0: never; 1 (default): the modes it 
  * BLOCKS of the frame with the most blocks for the rows geometries (rows / (64 * CPL / row width), rounded up; the
  * geometries that cut rows into segments: rows x segments) */
 long achip_uniform_extent(int mode, int variant, const achip_frame_t *frames, int n_frames) {
-  const int cpl = rows_variant_cpl(variant);
+  const int cpl = rows_cpl(variant);
   if (!cpl)
     return achip_max_cells(frames, n_frames);
   const bool hb = mode >= ACHIP_MODE_HB_TRUE && mode <= ACHIP_MODE_HB_MONO;
@@ -609,88 +614,111 @@ long achip_uniform_extent(int mode, int variant, const achip_frame_t *frames, in
     const long wp = (long)frames[i].pad_left + frames[i].out_w;
     const long rows = hb ? ((long)frames[i].out_h + 1) / 2 : frames[i].out_h;
     const long rpb = wp > 0 ? (64L * cpl) / wp : 0;
-    const long blocks = rows_variant_wide_waves(variant) ? rows * rows_wide_segments(wp, cpl) : rpb > 0 ? (rows + rpb - 1) / rpb : 0;
+    const long blocks = rows_wide_waves(variant) ? rows * rows_wide_segments(wp, cpl) : rpb > 0 ? (rows + rpb - 1) / rpb : 0;
     if (blocks > most)
       most = blocks;
   }
   return most;
 }
 
-int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, bool palette_ascii_only,
-                          const int *variant_caps, int n_cus, int split_request, int forced_variant, int *variant,
-                          int *parts, int *rows_per_part) {
-  const bool hb = mode >= ACHIP_MODE_HB_TRUE && mode <= ACHIP_MODE_HB_MONO;
-  int max_wp = 0, max_rows = 0;
-  for (int i = 0; i < n_frames; i++) {
-    const int wp = frames[i].pad_left + frames[i].out_w;
-    const int rows = hb ? (frames[i].out_h + 1) / 2 : frames[i].out_h;
-    if (wp > max_wp)
-      max_wp = wp;
-    if (rows > max_rows)
-      max_rows = rows;
+/* What every rule of the geometry policy reads: the launch, and facts of its frames gathered in one pass. */
+typedef struct {
+  int mode, n_frames, n_cus, split_request;
+  const achip_frame_t *frames;
+  int max_wp, max_rows, max_src_w, ghost; /* widest padded row, most text rows, widest single source */
+  long max_cells;                         /* (achip_max_cells) */
+  bool hb, general_sampler, dense, big_src, u8_true, cell_mode, run_mode, lean_true, short_tokens, shared_gpu, may_split;
+} launch_facts_t;
+
+static launch_facts_t launch_facts(int mode, const achip_frame_t *frames, int n_frames, bool palette_ascii_only, int n_cus,
+                                   int split_request) {
+  launch_facts_t F = {.mode = mode, .n_frames = n_frames, .n_cus = n_cus < 1 ? 256 : n_cus, .split_request = split_request,
+                      .frames = frames, .dense = true, .hb = mode >= ACHIP_MODE_HB_TRUE && mode <= ACHIP_MODE_HB_MONO};
+  for (int i = 0; i < n_frames; i++) { /* (general_sampler: composites / 1x1 sources; dense: every source IS the image its target samples) */
+    const achip_frame_t *f = &frames[i];
+    const int wp = f->pad_left + f->out_w, rows = F.hb ? (f->out_h + 1) / 2 : f->out_h;
+    const long cells = (long)wp * (long)f->out_h;
+    F.max_wp = wp > F.max_wp ? wp : F.max_wp;
+    F.max_rows = rows > F.max_rows ? rows : F.max_rows;
+    F.max_cells = cells > F.max_cells ? cells : F.max_cells;
+    if (!f->comp && f->src_w > F.max_src_w)
+      F.max_src_w = f->src_w;
+    F.general_sampler |= f->comp != NULL || (long)f->src_w * (long)f->src_h == 1;
+    F.dense &= !f->comp && f->src_w == f->out_w && f->src_h == f->out_h;
   }
-  *parts = 1;
-  *rows_per_part = max_rows > 0 ? max_rows : 1;
-  if (n_cus < 1)
-    n_cus = 256;
-  /* Whole-frame geometries (measured on MI355X, profiles/r01_split_sweep.txt, r01_overlap.txt): up to ~1.5
-   * workgroups per CU the 1024-thread x 2-cell geometry (4) has the shortest per-frame latency chain; with more
-   * frames than that in flight -- one large launch, or several launches kept in flight on separate streams, in which
-   * case the caller passes its share of the CUs -- two or three 512-thread workgroups per CU overlap each other's
-   * gather (HBM-bound) and token (latency-bound) phases instead.  Not the half-block modes: their kernels need more
-   * than 128 VGPRs in the small geometries and lose more than the overlap gains. */
-  /* The per-cell renderers (truecolor / 256 / 16 foreground, truecolor background; truecolor-fg with an all-ASCII
-   * palette) have no run structure: whole-frame launches of them take the wave-autonomous stream kernel
-   * (render_stream.hpp), whose waves gather, tokenise and drain independently -- no chunk, so no row-width limit,
-   * only a bound on the cells of a frame.  ACHIP_STREAM_* below restate render_variants.h / render_stream.hpp. */
-  const long max_cells = achip_max_cells(frames, n_frames);
-  int max_src_w = 0;
-  bool general_sampler = false, dense = true; /* composites / 1x1 sources; every source IS the image its target samples */
-  for (int i = 0; i < n_frames; i++) {
-    if (!frames[i].comp && frames[i].src_w > max_src_w)
-      max_src_w = frames[i].src_w;
-    general_sampler |= frames[i].comp != NULL || (long)frames[i].src_w * (long)frames[i].src_h == 1;
-    dense &= !frames[i].comp && frames[i].src_w == frames[i].out_w && frames[i].src_h == frames[i].out_h;
-  }
+  F.big_src = F.max_src_w > 1920;
   /* truecolor foreground with a palette that holds multi-byte glyphs (round 6: the stream kernel's instantiation of its own,
    * render_stream.hpp ACHIP_STREAM_MODE_TRUE_FG_U8): whole frames of single sources in geometries 16 / 17, never shared out
    * over workgroups (its RLE state crosses blocks through LDS words); composites and 1x1 sources stay with the phase kernel */
-  const bool u8_true = mode == ACHIP_MODE_TRUE_FG && !palette_ascii_only;
-  const bool cell_mode = mode == ACHIP_MODE_256_FG || mode == ACHIP_MODE_16_FG || mode == ACHIP_MODE_TRUE_BG ||
-                         (mode == ACHIP_MODE_TRUE_FG && (palette_ascii_only || !general_sampler));
-  const bool stream_forced = forced_variant >= ACHIP_HOST_STREAM_FIRST && forced_variant < ACHIP_HOST_ROWS_FIRST;
-  /* cells a block owns: 64 per lane slot, minus the ghost slot of truecolor-fg (render_stream.hpp: SLds::EFF) */
-  const int ghost = mode == ACHIP_MODE_TRUE_FG ? 1 : 0;
-  if (stream_forced) {
-    const int cpl = forced_variant == 19 || forced_variant == 20 ? 1 : 2;
-    if (!cell_mode || forced_variant > 20 || max_cells > (long)ACHIP_HOST_STREAM_MAXBLK * (64 * cpl - ghost))
-      return -1;
-    if (u8_true && forced_variant != 16 && forced_variant != 17 && forced_variant != 20)
-      return -1;
-    *variant = forced_variant;
-    return 0; /* whole frames only */
-  }
+  F.u8_true = mode == ACHIP_MODE_TRUE_FG && !palette_ascii_only;
+  /* The per-cell renderers (truecolor / 256 / 16 foreground, truecolor background; truecolor-fg with an all-ASCII
+   * palette) have no run structure: whole-frame launches of them take the wave-autonomous stream kernel
+   * (render_stream.hpp), whose waves gather, tokenise and drain independently -- no chunk, so no row-width limit,
+   * only a bound on the cells of a frame. */
+  F.cell_mode = mode == ACHIP_MODE_256_FG || mode == ACHIP_MODE_16_FG || mode == ACHIP_MODE_TRUE_BG ||
+                (mode == ACHIP_MODE_TRUE_FG && (palette_ascii_only || !F.general_sampler));
   /* The run-structured renderers (mono, half blocks) start a run at every row's first cell, so a whole number of text
    * rows is a self-contained block that ONE wave can take through the path (render_rows.hpp): whole-frame launches of
    * them take that kernel whenever the widest padded row fits a block (64 * CPL cells). */
   /* (... and whose sources are at most 21 845 pixels wide: render_rows.hpp keeps a sample's byte offset in 16 bits) */
-  const bool run_mode = (mode == ACHIP_MODE_MONO || hb) && max_src_w <= 21845;
-  if (forced_variant >= ACHIP_HOST_ROWS_FIRST) {
-    const int cpl = rows_variant_cpl(forced_variant);
-    if (!run_mode || !cpl || max_wp > rows_variant_max_row(forced_variant) || achip_uniform_extent(mode, forced_variant, frames, n_frames) > ACHIP_HOST_STREAM_MAXBLK)
-      return -1;
-    if ((forced_variant == 26 || rows_variant_wide_waves(forced_variant) || rows_variant_parts(forced_variant)) && general_sampler) /* (geometry 26, the segment geometries and the shared-out one carry the fast sampler only) */
-      return -1;
-    *variant = forced_variant;
-    return 0; /* whole frames only */
-  }
-  /* automatic: whenever whole frames are launched anyway (the split policy below decides that first) */
+  F.run_mode = (mode == ACHIP_MODE_MONO || F.hb) && F.max_src_w <= 21845;
+  F.lean_true = mode == ACHIP_MODE_TRUE_FG && palette_ascii_only && !F.general_sampler;
+  F.short_tokens = mode == ACHIP_MODE_MONO || mode == ACHIP_MODE_HB_MONO;
+  F.shared_gpu = F.n_cus <= 128;
+  F.ghost = mode == ACHIP_MODE_TRUE_FG ? 1 : 0; /* cells a block owns: 64 per lane slot, minus the ghost slot of truecolor-fg
+                                                   (render_stream.hpp: SLds::EFF) */
   /* automatic splitting only when whole frames would leave CUs idle: below 3/4 frame per CU -- the half-block modes below
    * half a frame per CU (round 4 audit: 128 frames of 120x40, one launch at a time: mono half blocks 23.9 us in three
    * bands each against 19.8 whole, 256 colours 29.3 against 26.8; 64 frames: 14.0 against 28.4 the other way) */
-  const bool whole_auto = split_request == 0 && (4 * n_frames >= 3 * n_cus || (hb && 2 * n_frames >= n_cus));
-  const bool may_split = mode != ACHIP_MODE_16_DITHER_BG && !(mode == ACHIP_MODE_TRUE_FG && !palette_ascii_only) &&
-                         split_request >= 0 && max_rows > 1 && !whole_auto;
+  const bool whole_auto = split_request == 0 && (4 * n_frames >= 3 * F.n_cus || (F.hb && 2 * n_frames >= F.n_cus));
+  /* Row bands.  Never for the serial dither, nor for truecolor-fg with multi-byte glyphs (its RLE state would
+   * have to be searched backwards across bands).  Automatic splitting only when whole frames would leave CUs
+   * idle (fewer than 3/4 frame per CU): at one frame per CU and above it costs more than it gains. */
+  F.may_split = mode != ACHIP_MODE_16_DITHER_BG && !F.u8_true && split_request >= 0 && F.max_rows > 1 && !whole_auto;
+  return F;
+}
+
+static long extent(const launch_facts_t *F, int variant) { return achip_uniform_extent(F->mode, variant, F->frames, F->n_frames); }
+
+/* Whether a forced geometry can render the launch, for all three families; ids that are no geometry are refused.  The
+ * stream and rows geometries then render whole frames only; a phase geometry may still be cut into row bands. */
+static bool forced_applies(const launch_facts_t *F, const int *variant_caps, int id) {
+  if (id >= 0 && id < ACHIP_VARIANT_COUNT) /* (no half-block instantiations in the 512- / 256-thread geometries: render_inst.hip has_mode) */
+    return F->max_wp <= variant_caps[id] && !(F->hb && (id == 1 || id == 2));
+  if (stream_cpl(id)) /* (truecolor-fg with multi-byte glyphs: render_stream_inst.hip HAS_U8) */
+    return F->cell_mode && F->max_cells <= (long)ACHIP_STREAM_MAXBLK * (64 * stream_cpl(id) - F->ghost) &&
+           !(F->u8_true && id != 16 && id != 17 && id != 20);
+  if (rows_cpl(id)) /* (geometry 26, the segment geometries and the shared-out ones carry the fast sampler only) */
+    return F->run_mode && F->max_wp <= rows_max_row(id) && extent(F, id) <= ACHIP_STREAM_MAXBLK &&
+           !(F->general_sampler && (id == 26 || rows_wide_waves(id) || ACHIP_ROWS_VARIANT_PARTS(id)));
+  return false;
+}
+
+/* How many workgroups a frame's `units` (blocks, or rows of blocks) are shared out over, `per_part` units each (a wave per
+ * block): at least min(units, least), at most 64, and no more than let every workgroup of the launch have a CU to itself;
+ * `env` (a diagnostics switch), where the CUs allow it, instead.  1 when the launch is not shared out: fewer than two parts,
+ * or a wave with more than ONE block -- a workgroup can publish its byte count only when its LAST block is scanned, so with
+ * a second round per wave every part waits for the part in front of it to finish its first: the parts run one after the
+ * other (sixteen 200x60 frames in 16 parts of six blocks: 53 us against 9.9 as row bands; 128 80x24 frames in two parts
+ * each: 11.7 against 7.0 whole; profiles/r04_small_batch_parts.txt) */
+static int shared_parts(const launch_facts_t *F, long units, int per_part, int least, int env) {
+  long np = per_part > 0 ? (units + per_part - 1) / per_part : 0;
+  if (np < least)
+    np = units < least ? units : least;
+  if (np > 64)
+    np = 64;
+  if (np * F->n_frames > F->n_cus)
+    np = F->n_cus / F->n_frames;
+  if (env >= 1 && env <= 64 && (long)env * F->n_frames <= F->n_cus)
+    np = env;
+  return np >= 2 && (units + np - 1) / np <= per_part ? (int)np : 1;
+}
+
+/* the stream kernel (per-cell modes): 18 shared out, then 16 / 17 whole frames; false: no choice */
+static bool stream_choice(const launch_facts_t *F, const int *variant_caps, int *variant, int *parts) {
+  const long blk = 128 - F->ghost; /* cells of a block of the automatic geometries (two per lane) */
+  if (!F->cell_mode || F->max_cells > ACHIP_STREAM_MAXBLK * blk)
+    return false;
   /* frames small enough for ONE block per wave of a wave-autonomous geometry are never cut into row bands, however few
    * they are: a lone 80x24 frame takes 6.3 us through stream geometry 16 against 8.4 us as 24 bands of the phase kernel
    * whose workgroups hand their offsets to each other through global memory, a lone mono frame 7.0 against 8.1 us through
@@ -701,36 +729,15 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
    * allow), as long as every workgroup of the launch has a CU to itself (they hand their byte counts to each other
    * through memory, so all of them must be resident): one workgroup per frame queues all of the frame's waves on the
    * four SIMDs of ONE CU (profiles/r04_lone_frame_timeline.txt). */
-  if (forced_variant < 0 && cell_mode && !u8_true && split_request == 0 && max_cells <= (long)ACHIP_HOST_STREAM_MAXBLK * (128 - ghost)) {
-    const long nblk = (max_cells + (128 - ghost) - 1) / (128 - ghost);
-    /* four blocks per workgroup (a wave each), but up to sixteen workgroups for a small frame (a lone 80x24 frame: 5.8 us
-     * in 16 parts of one block, 5.9 in four; more than that loses again: 4K -> 200x60 in 64 parts 7.2 us against 6.9 in 24,
-     * the grid's nine targets 8.6 in 28 against 8.0 in 16 -- the first block of a part polls every part in front of it) */
-    long np = (nblk + 3) / 4;
-    if (np < 16)
-      np = nblk < 16 ? nblk : 16;
-    if (np > 64)
-      np = 64;
-    if (np * n_frames > n_cus)
-      np = n_cus / n_frames;
-    { /* ASCIICHAT_HIP_STREAM_PARTS (diagnostics, read once): 1 = never, N = this many where the CUs allow */
-      static _Atomic int forced_cache = -1;
-      const int forced = env_int_once(&forced_cache, "ASCIICHAT_HIP_STREAM_PARTS");
-      if (forced >= 1 && forced <= 64 && (long)forced * n_frames <= n_cus)
-        np = forced;
-    }
-    /* only while every wave has at most ONE block: a workgroup can publish its byte count only when its LAST block is
-     * scanned, so with a second round per wave every part waits for the part in front of it to finish its first -- the
-     * parts run one after the other (sixteen 200x60 frames in 16 parts of six blocks: 53 us against 9.9 as row bands; 128
-     * 80x24 frames in two parts each: 11.7 against 7.0 whole; profiles/r04_small_batch_parts.txt) */
-    if (np >= 2 && (nblk + np - 1) / np <= 4) {
-      *variant = 18;
-      *parts = (int)np;
-      *rows_per_part = 1;
-      return 0;
-    }
+  /* (four blocks per workgroup (a wave each), but up to sixteen workgroups for a small frame (a lone 80x24 frame: 5.8 us
+   * in 16 parts of one block, 5.9 in four; more than that loses again: 4K -> 200x60 in 64 parts 7.2 us against 6.9 in 24,
+   * the grid's nine targets 8.6 in 28 against 8.0 in 16 -- the first block of a part polls every part in front of it)) */
+  if (!F->u8_true && F->split_request == 0 &&
+      (*parts = shared_parts(F, (F->max_cells + blk - 1) / blk, 4, 16, stream_parts_forced())) > 1) {
+    *variant = 18;
+    return true;
   }
-  const bool one_block_per_wave = cell_mode && split_request == 0 && max_cells <= 16 * (128 - ghost);
+  const bool one_block_per_wave = F->split_request == 0 && F->max_cells <= 16 * blk;
   /* (round 4 audit: from half a frame per CU on, frames of at most three blocks per wave of the sixteen-wave geometry go
    * whole too -- 128 frames of 120x40, one launch at a time: 12.9 us whole against 16.8 as three bands each) */
   /* (round 6, after the stream kernel's lean loop -- scripts/gpu_truecolor_half_cu.py, profiles/r06_whole_from_three_eighths.txt,
@@ -741,70 +748,59 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
    * (16.8 / 19.8).  The other per-cell modes, frames of at most four blocks per wave (160x45), from 3/8 too: 256 colours 96 frames
    * of 120x40 10.1 / 13.4, 160x45 13.0 / 13.6, 128 frames 13.3 / 14.5; larger frames keep their bands up to 3/4 (200x60, 128
    * frames: 22.6 whole against 18.8)) */
-  const bool lean_true = mode == ACHIP_MODE_TRUE_FG && palette_ascii_only && !general_sampler;
   /* (... and truecolor frames of at most four blocks per wave already from 5/16: 80 frames of 120x40 9.7 against 11.0, 160x45
    * 12.6 against 15.9; at 64 frames 160x45 is behind its bands, 12.6 against 11.6) */
-  const bool four_blocks = max_cells <= 4 * 16 * (128 - ghost);
-  const bool few_blocks = cell_mode && split_request == 0 &&
-                          ((8 * n_frames >= 3 * n_cus && (lean_true || four_blocks)) || (16 * n_frames >= 5 * n_cus && lean_true && four_blocks));
-  if (forced_variant < 0 && cell_mode && (!may_split || max_wp > variant_caps[0] || one_block_per_wave || few_blocks) &&
-      max_cells <= (long)ACHIP_HOST_STREAM_MAXBLK * (128 - ghost)) {
-    /* measured (profiles/r02_stream_sweep.txt): 1024 threads x 2 cells -- one block per wave for a 1080p -> 80x24
-     * frame -- is the shortest single launch while every frame has a CU to itself; with more frames than CUs in
-     * flight (a large batch, or several launches kept in flight: the caller passes its share of the CUs), or frames
-     * of several blocks per wave, 512-thread workgroups pack better (four launches in flight, us per step, 16 vs 17: 1080p -> 80x24 truecolor
-     * 10.9 vs 8.2, ANSI-256 7.0 vs 6.6, 4K -> 200x60 equal within noise) */
-    /* round 4 audit (scripts/gpu_policy_audit.py, profiles/r04_policy_audit.txt: six terminal sizes x five batch sizes x
-     * four modes, every geometry forced in turn): the rule is the FRAMES PER CU, not the blocks per wave -- with at most a
-     * frame per CU of the plan's share a CU holds ONE workgroup either way, and sixteen waves fill it better than eight
-     * however many blocks each walks (256 frames, one launch at a time: 120x40 truecolor 17.3 vs 22.3 us, 200x60 34.1 vs
-     * 43.4, 320x90 71.7 vs 94.2; 64 frames with four launches in flight: 20.9 vs 26.1 at 200x60); above that two
-     * 512-thread workgroups share a CU and win or tie (256 frames, four in flight: 35.7 vs 36.9 at 200x60). */
-    /* (up to TWO frames per CU: 128 frames at a share of 64 CUs, 200x60: 23.5 vs 29.6 us; at three they tie, at four
-     * the 512-thread workgroups win by 3-10 %) */
-    /* (round 6's last audit, AUDIT_BATCHES=320..2048 of scripts/gpu_policy_audit.py, profiles/r06_whole_from_three_eighths.txt: with
-     * the GPU to itself, between one and two frames per CU, frames of more than one block per wave pack better as 512-thread
-     * workgroups -- 512 frames of 120x40 21.2-22.9 us against 28.1-29.2, 160x45 26.6-28.4 against 34.3-35.1; 320 / 384 / 512 frames of 200x60 truecolor 36.3 / 37.5 / 40.8 us against 41.3 / 42.3 / 49.9, 320x90 80.1-86.4 against
-     * 87.0-96.7, 640x90 150.8-162.2 against 168.3-182.5, 256 colours 13-22 %; 80x24 frames level; at a share of 64 CUs two frames per
-     * CU stay level between the two) */
-    const bool big_alone = n_cus > 128 && n_frames > n_cus && max_cells > 16L * (128 - ghost);
-    *variant = n_frames <= 2 * n_cus && !big_alone ? 16 : 17;
-    return 0;
-  }
-  /* (the coloured half-block modes only from a frame per four CUs on: their tokens are long -- two SGRs and a three-byte glyph
-   * per cell -- and a rows-kernel block is ONE wave taking its cells through the path four at a time, so with few frames the
-   * row bands of the phase kernel, a thread per cell, are shorter: a lone 80x24 half-block truecolor frame 9.0 us as bands
-   * against 12.6 whole, eight of them 9.7 against 12.9, sixty-four in four bands each 10.2 against 13.3, ninety-six 17.9 against
-   * 13.4; profiles/r04_small_run_modes.txt) */
-  const bool short_tokens = mode == ACHIP_MODE_MONO || mode == ACHIP_MODE_HB_MONO;
+  const bool four_blocks = F->max_cells <= 4 * 16 * blk;
+  const bool few_blocks = F->split_request == 0 && ((8 * F->n_frames >= 3 * F->n_cus && (F->lean_true || four_blocks)) ||
+                                                    (16 * F->n_frames >= 5 * F->n_cus && F->lean_true && four_blocks));
+  if (F->may_split && F->max_wp <= variant_caps[0] && !one_block_per_wave && !few_blocks)
+    return false;
+  /* measured (profiles/r02_stream_sweep.txt): 1024 threads x 2 cells -- one block per wave for a 1080p -> 80x24
+   * frame -- is the shortest single launch while every frame has a CU to itself; with more frames than CUs in
+   * flight (a large batch, or several launches kept in flight: the caller passes its share of the CUs), or frames
+   * of several blocks per wave, 512-thread workgroups pack better (four launches in flight, us per step, 16 vs 17: 1080p -> 80x24 truecolor
+   * 10.9 vs 8.2, ANSI-256 7.0 vs 6.6, 4K -> 200x60 equal within noise) */
+  /* round 4 audit (scripts/gpu_policy_audit.py, profiles/r04_policy_audit.txt: six terminal sizes x five batch sizes x
+   * four modes, every geometry forced in turn): the rule is the FRAMES PER CU, not the blocks per wave -- with at most a
+   * frame per CU of the plan's share a CU holds ONE workgroup either way, and sixteen waves fill it better than eight
+   * however many blocks each walks (256 frames, one launch at a time: 120x40 truecolor 17.3 vs 22.3 us, 200x60 34.1 vs
+   * 43.4, 320x90 71.7 vs 94.2; 64 frames with four launches in flight: 20.9 vs 26.1 at 200x60); above that two
+   * 512-thread workgroups share a CU and win or tie (256 frames, four in flight: 35.7 vs 36.9 at 200x60). */
+  /* (up to TWO frames per CU: 128 frames at a share of 64 CUs, 200x60: 23.5 vs 29.6 us; at three they tie, at four
+   * the 512-thread workgroups win by 3-10 %) */
+  /* (round 6's last audit, AUDIT_BATCHES=320..2048 of scripts/gpu_policy_audit.py, profiles/r06_whole_from_three_eighths.txt: with
+   * the GPU to itself, between one and two frames per CU, frames of more than one block per wave pack better as 512-thread
+   * workgroups -- 512 frames of 120x40 21.2-22.9 us against 28.1-29.2, 160x45 26.6-28.4 against 34.3-35.1; 320 / 384 / 512 frames of 200x60 truecolor 36.3 / 37.5 / 40.8 us against 41.3 / 42.3 / 49.9, 320x90 80.1-86.4 against
+   * 87.0-96.7, 640x90 150.8-162.2 against 168.3-182.5, 256 colours 13-22 %; 80x24 frames level; at a share of 64 CUs two frames per
+   * CU stay level between the two) */
+  const bool big_alone = F->n_cus > 128 && F->n_frames > F->n_cus && F->max_cells > 16 * blk;
+  *variant = F->n_frames <= 2 * F->n_cus && !big_alone ? 16 : 17;
+  return true;
+}
+
+/* the rows kernel (run-structured modes): 31 / 32 shared out, 25 for a small launch, 24 / 25 / 26 and the wide rows' 27 / 29
+ * whole frames; false: no choice */
+static bool rows_choice(const launch_facts_t *F, const int *variant_caps, int *variant, int *parts) {
+  if (!F->run_mode)
+    return false;
+  const int mode = F->mode, max_wp = F->max_wp, n_frames = F->n_frames, n_cus = F->n_cus;
+  const bool small = F->may_split && F->split_request == 0; /* a launch the row bands would cut */
   /* Small launches of the run-structured modes (round 6) -- a lone mono frame, a few half-block frames --
    * share a frame's blocks out over four-wave workgroups of the rows kernel (render_rows.hpp PARTS, geometry 31: 128-cell
-   * blocks -- ONE text row at 80 or 120 columns --, one block per wave) as the per-cell modes do above, while every workgroup
-   * of the launch has a CU to itself.  Measured (scripts/gpu_r6_k.sh, profiles/r06_small_rows_parts.txt; one launch after the
-   * other, us per launch): a lone 80x24 mono frame 6.5 against 7.6 whole on geometry 25 and 7.5-8.2 as row bands; a lone
-   * half-block truecolor frame 8.3 against 9.0-9.4 as bands (11.6 whole); eight frames 7.4 / 9.2 against 8.0 / 9.7.  With
+   * blocks -- ONE text row at 80 or 120 columns --, one block per wave) as the per-cell modes do in stream_choice, while every
+   * workgroup of the launch has a CU to itself.  Measured (scripts/gpu_r6_k.sh, profiles/r06_small_rows_parts.txt; one launch
+   * after the other, us per launch): a lone 80x24 mono frame 6.5 against 7.6 whole on geometry 25 and 7.5-8.2 as row bands; a
+   * lone half-block truecolor frame 8.3 against 9.0-9.4 as bands (11.6 whole); eight frames 7.4 / 9.2 against 8.0 / 9.7.  With
    * 256-cell blocks (three rows each, two workgroups) nothing is gained: the shorter block shortens the chain, not the idle
    * SIMDs. */
   /* (rows of 129-256 cells as ONE row per block of four cell slots were measured too -- scripts/gpu_r6_n.sh: a lone 160x48 mono
    * frame 8.2 us against the row bands' 8.1-8.3, half-block truecolor 11.1 against 9.8-10.0, 200x60 12.6 against 10.1 -- and
    * lost: the block is what a wave walks alone, and 160 cells are twice 80.  Such rows are cut into segments instead: below) */
-  if (forced_variant < 0 && run_mode && !general_sampler && may_split && split_request == 0 && max_wp <= 64 * ACHIP_ROWS_PARTS_CPL) {
-    const long nblk = achip_uniform_extent(mode, 31, frames, n_frames);
-    long np = (nblk + 3) / 4;
-    if (np > 64)
-      np = 64;
-    if (np * n_frames > n_cus)
-      np = n_cus / n_frames;
-    {
-      const int forced = rows_parts_forced();
-      if (forced >= 1 && forced <= 64 && (long)forced * n_frames <= n_cus)
-        np = forced;
-    }
-    if (np >= 2 && nblk > 0 && (nblk + np - 1) / np <= 4) {
+  if (small && !F->general_sampler && max_wp <= rows_max_row(31)) {
+    const long nblk = extent(F, 31);
+    if (nblk > 0 && (*parts = shared_parts(F, nblk, 4, 0, rows_parts_forced())) > 1) {
       *variant = 31;
-      *parts = (int)np;
-      *rows_per_part = 1;
-      return 0;
+      return true;
     }
   }
   /* ... and rows of 129-512 cells cut into at most four segments of at most 128 cells, WHOLE rows per four-wave workgroup
@@ -816,34 +812,28 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
    * 8.3-8.5 (256x30), 3-11 % ahead everywhere; mono half blocks 2-10 % ahead; truecolor half blocks level to 6 % ahead (9.8
    * against 9.9, 9.1 against 9.7 at 256x30; never more than 0.5 % behind); the 256- / 16-colour half blocks 6-20 % BEHIND
    * (byte-built tokens of one wave against a thread per cell: 9.7 against 9.0, 11.3 against 9.4) -- those keep their bands. */
-  const bool parts_wide_mode = short_tokens || mode == ACHIP_MODE_HB_TRUE || rows_parts_wide_level() == 2;
-  if (forced_variant < 0 && run_mode && parts_wide_mode && !general_sampler && may_split && split_request == 0 && rows_parts_wide_level() != 0 &&
-      max_wp > 64 * ACHIP_ROWS_PARTS_CPL && max_wp <= rows_variant_max_row(32)) {
-    const long nseg = rows_wide_segments(max_wp, rows_variant_cpl(32));
-    const long rpw = nseg > 0 ? 4 / nseg : 0; /* rows of a workgroup */
-    long np = rpw > 0 ? (max_rows + rpw - 1) / rpw : 0;
-    if (np > 64)
-      np = 64;
-    if (np * n_frames > n_cus)
-      np = n_cus / n_frames;
-    {
-      const int forced = rows_parts_forced();
-      if (forced >= 1 && forced <= 64 && (long)forced * n_frames <= n_cus)
-        np = forced;
-    }
-    if (np >= 2 && ((max_rows + np - 1) / np) * nseg <= 4 && achip_uniform_extent(mode, 32, frames, n_frames) <= ACHIP_HOST_STREAM_MAXBLK) {
+  const bool parts_wide_mode = F->short_tokens || mode == ACHIP_MODE_HB_TRUE || rows_parts_wide_level() == 2;
+  if (small && parts_wide_mode && !F->general_sampler && rows_parts_wide_level() != 0 && max_wp > rows_max_row(31) &&
+      max_wp <= rows_max_row(32)) {
+    const long nseg = rows_wide_segments(max_wp, rows_cpl(32));
+    const int rpw = nseg > 0 ? (int)(4 / nseg) : 0; /* rows of a workgroup */
+    if (extent(F, 32) <= ACHIP_STREAM_MAXBLK && (*parts = shared_parts(F, F->max_rows, rpw, 0, rows_parts_forced())) > 1) {
       *variant = 32;
-      *parts = (int)np;
-      *rows_per_part = 1;
-      return 0;
+      return true;
     }
   }
-  if (forced_variant < 0 && run_mode && may_split && split_request == 0 && max_wp <= 256 &&
-      (short_tokens || 4 * n_frames > n_cus) && achip_uniform_extent(mode, 25, frames, n_frames) <= 8) {
-    *variant = 25; /* one block of whole rows per wave of its eight: see above */
-    return 0;
+  /* (the coloured half-block modes only from a frame per four CUs on: their tokens are long -- two SGRs and a three-byte glyph
+   * per cell -- and a rows-kernel block is ONE wave taking its cells through the path four at a time, so with few frames the
+   * row bands of the phase kernel, a thread per cell, are shorter: a lone 80x24 half-block truecolor frame 9.0 us as bands
+   * against 12.6 whole, eight of them 9.7 against 12.9, sixty-four in four bands each 10.2 against 13.3, ninety-six 17.9 against
+   * 13.4; profiles/r04_small_run_modes.txt) */
+  if (small && max_wp <= rows_max_row(25) && (F->short_tokens || 4 * n_frames > n_cus) && extent(F, 25) <= 8) {
+    *variant = 25; /* one block of whole rows per wave of its eight: see stream_choice */
+    return true;
   }
-  if (forced_variant < 0 && run_mode && !may_split && max_wp <= 64 * 7) {
+  if (F->may_split)
+    return false;
+  if (max_wp <= rows_max_row(24)) {
     /* the geometry whose blocks waste fewer lane slots on this row width; the smaller one on a tie.  Measured
      * (profiles/r03_rows_kernel.txt, 256 frames per launch): 1080p -> 80x24 half blocks 15.7 us per step with four
      * launches in flight / 22.6 one at a time (phase kernel: 22.6 / 24.1); 4K -> 400x120 half blocks 212 us with four in
@@ -855,18 +845,18 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
      * four-slot geometry wins whatever the slots it wastes -- its workgroups need fewer registers and more of them share a
      * CU: 256 mono frames of 160x45 at a share of 64 CUs 14.3 against 17.3 us, 200x60 20.7 against 24.7, half-block
      * truecolor 38.4 against 40.8; at two frames per CU the seven-slot one is still ahead, 9.0 against 10.6) */
-    if (short_tokens && max_wp <= 256 && n_frames > 2 * n_cus) /* (mono and mono half blocks, 200x60: 29.0 against 35.3; the coloured
-                                                                   half-block modes differ by -14 .. +5 % and keep the slot rule) */
+    if (F->short_tokens && max_wp <= 256 && n_frames > 2 * n_cus) /* (mono and mono half blocks, 200x60: 29.0 against 35.3; the coloured
+                                                                      half-block modes differ by -14 .. +5 % and keep the slot rule) */
       v = 25;
     /* (round 5, word-built SGRs: truecolor half blocks from full-frame sources on a shared GPU as well -- 256 frames at a
      * share of 64 CUs, 1080p -> 160x45 35.8 against 39.0 us, 200x60 53.8 against 57.5, 4K -> 200x60 76.4 against 79.7; from
      * dense sources the seven-slot geometry keeps its 0-7 %: profiles/r05_policy_audit_hb.txt) */
-    if (mode == ACHIP_MODE_HB_TRUE && !dense && n_cus <= 128 && max_wp <= 256 && n_frames > n_cus)
+    if (mode == ACHIP_MODE_HB_TRUE && !F->dense && n_cus <= 128 && max_wp <= 256 && n_frames > n_cus)
       v = 25;
     /* (round 4 audit: the coloured half-block modes at no more than a frame per CU only while a wave has ONE block --
      * 256 frames of 120x40, one launch at a time: 42.9 us against the phase kernel's 37.5, 238x70 104 against 95; 80x24,
      * four blocks a frame, 21.2 against 23.1.  Mono keeps the rows kernel: 238x70 47 against 52.) */
-    const int ext = achip_uniform_extent(mode, v, frames, n_frames);
+    const int ext = extent(F, v);
     /* (... the half-block mono mode as well: 256 frames of 238x70 64 against 53; above a frame per CU the rows kernel
      * wins for all of them -- 4K -> 400x120, 128 frames at a share of 64 CUs, bench.py's schedule: 108 against 118;
      * mono rows wider than the four-slot geometry take the seven-slot one at any count: 256 frames of 320x90 79 against 88) */
@@ -876,7 +866,6 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
      * on the phase kernel against 17.3, 320x90 22.6 against 27.1; with the GPU to itself the rows kernel stays ahead, above) */
     /* (the half-block modes' frames of one block per wave as well: 64 frames of 80x24 at a share of 64 CUs 5.2-5.9 us on the
      * phase kernel against 6.2-6.9, all four of them) */
-    const bool shared_gpu = n_cus <= 128;
     /* (round 5: ... or the seven-slot geometry as ONE sixteen-wave workgroup per frame (26), which fills a CU the way two
      * eight-wave workgroups of two launches do.  First measured for dense sources and rows wider than the four-slot
      * geometry (256 frames of 400x240 -> 400x120 truecolor half blocks, one launch at a time: 195.9 us against the phase
@@ -897,8 +886,7 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
      * 320x90 59.5 against 81.9, dense 160x45 18.8 against 25.0; 64 frames at a share of 64 CUs: 200x60 7.9 against 10.0,
      * 320x90 15.6 against 22.6; mono half blocks from dense sources 7-28 %, from full frames only beyond the four-slot
      * geometry: 320x90 76.7 against 86.6, 200x60 48.0 against 41.5 the other way) */
-    if (!general_sampler && n_frames <= n_cus && achip_uniform_extent(mode, 26, frames, n_frames) <= ACHIP_HOST_STREAM_MAXBLK) {
-      const bool big_src = max_src_w > 1920;
+    if (!F->general_sampler && n_frames <= n_cus && extent(F, 26) <= ACHIP_STREAM_MAXBLK) {
       bool take26;
       /* (round 6, the audit again with this round's forms among the automatic choices, profiles/r06_policy_audit_run_modes.txt:
        * from sources up to 1080p already from 120 columns -- 192 mono frames of 120x40 17.8 against 19.7 us, 64 at a share of
@@ -908,34 +896,35 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
         /* (mono from 4K sources at a full frame per CU too -- round 6's last audit, 256 frames one launch at a time: 320x90 69.2 against
          * 90.7 us on geometry 24 and 87.2 on the phase kernel, 400x120 104.2 against 145.4 / 137.1; truecolor half blocks there are level:
          * BASELINE configs[4] 242-246 against the phase kernel's 248) */
-        take26 = dense ? max_wp >= 120 : !big_src ? max_wp >= 120
-                 : (max_wp > 256 && (shared_gpu || 4 * n_frames <= 3 * n_cus || mode == ACHIP_MODE_MONO));
+        take26 = F->dense ? max_wp >= 120 : !F->big_src ? max_wp >= 120
+                 : (max_wp > 256 && (F->shared_gpu || 4 * n_frames <= 3 * n_cus || mode == ACHIP_MODE_MONO));
       else if (mode == ACHIP_MODE_HB_MONO) /* (rows beyond the four-slot geometry on a shared GPU too -- round 6's last audit: 64 frames of
                                              * 320x90 at a share of 64 CUs 17.6 us against the phase kernel's 22.2, geometry 24 27.9) */
-        take26 = dense ? max_wp >= 120 : ((!shared_gpu && max_wp > 220) || max_wp > 256);
+        take26 = F->dense ? max_wp >= 120 : ((!F->shared_gpu && max_wp > 220) || max_wp > 256);
       else /* (... from dense sources already from 120 columns, audited again after quant16's diet, profiles/r06_policy_audit_hb16.txt:
               * 128-256 frames of 120x40, one launch at a time, 256 colours 22.9-23.5 against 26.5-27.2 us, 16 colours 24.5-25.4 against
               * 27.4-27.7; 64 frames at a share of 64 CUs 6.6 / 7.1 against 7.4 / 7.7) */
-        take26 = max_wp >= 200 || (max_wp >= 160 && (dense || 4 * n_frames <= 3 * n_cus)) || (dense && max_wp >= 120);
+        take26 = max_wp >= 200 || (max_wp >= 160 && (F->dense || 4 * n_frames <= 3 * n_cus)) || (F->dense && max_wp >= 120);
       /* (... but not from 4K sources from 3/4 frame per CU on while the four-slot geometry holds the rows: 192 / 256 frames of 4K -> 200x60,
        * 256 colours 70.8 / 86.0 us against the phase kernel's 65.5 / 79.5, 16 colours 73.1 / 87.8 against 66.8 / 78.1 -- the last audit) */
-      if ((mode == ACHIP_MODE_HB_256 || mode == ACHIP_MODE_HB_16) && big_src && max_wp <= 256 && 4 * n_frames >= 3 * n_cus)
+      if ((mode == ACHIP_MODE_HB_256 || mode == ACHIP_MODE_HB_16) && F->big_src && max_wp <= 256 && 4 * n_frames >= 3 * n_cus)
         take26 = false;
       if (take26) {
         *variant = 26;
-        return 0;
+        return true;
       }
     }
     /* (round 6's last audits: the 256- / 16-colour and mono half blocks of one block per wave take the rows kernel at no more than a frame
      * per CU from dense sources only -- from full-frame sources the phase kernel is 8-10 % ahead there: 128 / 192 / 256 frames of 1080p ->
      * 80x24, 256 colours 16.0 / 17.3 / 20.2 us against 17.4 / 18.7 / 21.0, 16 colours 16.0 / 17.3 / 19.7 against 17.3 / 19.1 / 21.8, mono
      * half blocks 12.4 against 13.4; truecolor half blocks the other way, 18.3 against 17.5) */
-    const bool take = n_frames > n_cus ? true : mono ? !(shared_gpu && ext > 8)
-                                                     : (ext <= 8 && !shared_gpu && (dense || mode == ACHIP_MODE_HB_TRUE));
-    if ((v == 25 || n_frames > n_cus || (mono && max_wp > 256)) && ext <= ACHIP_HOST_STREAM_MAXBLK && take) {
+    const bool take = n_frames > n_cus ? true : mono ? !(F->shared_gpu && ext > 8)
+                                                     : (ext <= 8 && !F->shared_gpu && (F->dense || mode == ACHIP_MODE_HB_TRUE));
+    if ((v == 25 || n_frames > n_cus || (mono && max_wp > 256)) && ext <= ACHIP_STREAM_MAXBLK && take) {
       *variant = v;
-      return 0;
+      return true;
     }
+    return false;
   }
   /* Rows beyond one block of the rows kernel (448 cells; round 6): cut into segments, a segment per wave (render_rows.hpp
    * WIDE) -- whole-frame launches of single sources; rows of up to 4096 cells as sixteen-wave workgroups (27), with more
@@ -945,34 +934,31 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
    * kernel by 15-45 % everywhere but one corner, mono on a shared GPU at up to two frames per CU of the share, where the
    * 512-thread phase geometry is 5-12 % ahead: 128 frames of 1000x40 at a share of 64 CUs 47.6 against 53.5 us) */
   const bool wide_corner = mode == ACHIP_MODE_MONO && n_cus <= 128 && n_frames > n_cus && n_frames <= 2 * n_cus && max_wp <= variant_caps[1];
-  if (forced_variant < 0 && run_mode && !may_split && !general_sampler && max_wp > 64 * 7 && !wide_corner) {
-    const int v = n_frames > n_cus && max_wp <= rows_variant_max_row(29) ? 29 : 27;
-    if (max_wp <= rows_variant_max_row(v) && achip_uniform_extent(mode, v, frames, n_frames) <= ACHIP_HOST_STREAM_MAXBLK) {
-      *variant = v;
-      return 0;
-    }
+  if (F->general_sampler || wide_corner)
+    return false;
+  const int v = n_frames > n_cus && max_wp <= rows_max_row(29) ? 29 : 27;
+  if (max_wp <= rows_max_row(v) && extent(F, v) <= ACHIP_STREAM_MAXBLK) {
+    *variant = v;
+    return true;
   }
-  if (forced_variant >= 0) {
-    if (max_wp > variant_caps[forced_variant])
-      return -1;
-    if (hb && (forced_variant == 1 || forced_variant == 2))
-      return -1; /* no half-block instantiations in the 512- / 256-thread geometries (render_inst.hip: has_mode) */
+  return false;
+}
+
+/* the phase kernel: geometry 0 / 1 / 4 (or the forced one), then row bands; -1 when no geometry holds a padded row */
+static int phase_choice(const launch_facts_t *F, const int *variant_caps, int forced_variant, int *variant, int *parts,
+                        int *rows_per_part) {
+  const int max_wp = F->max_wp, max_rows = F->max_rows, n_frames = F->n_frames, n_cus = F->n_cus;
+  if (forced_variant >= 0)
     *variant = forced_variant;
-  } else if (!hb && n_frames > (3 * n_cus) / 2 && max_wp <= variant_caps[1]) {
+  else if (!F->hb && n_frames > (3 * n_cus) / 2 && max_wp <= variant_caps[1])
     *variant = 1;
-  } else if (max_wp <= variant_caps[4]) {
+  else if (max_wp <= variant_caps[4])
     *variant = 4;
-  } else if (max_wp <= variant_caps[0]) {
+  else if (max_wp <= variant_caps[0])
     *variant = 0;
-  } else {
+  else
     return -1;
-  }
-  /* Row bands.  Never for the serial dither, nor for truecolor-fg with multi-byte glyphs (its RLE state would
-   * have to be searched backwards across bands).  Automatic splitting only when whole frames would leave CUs
-   * idle (fewer than 3/4 frame per CU): at one frame per CU and above it costs more than it gains. */
-  const bool splittable = mode != ACHIP_MODE_16_DITHER_BG && !(mode == ACHIP_MODE_TRUE_FG && !palette_ascii_only) &&
-                          split_request >= 0 && max_rows > 1;
-  if (!splittable || whole_auto)
+  if (!F->may_split)
     return 0;
   if (forced_variant >= 0 && forced_variant != 1 && forced_variant != 2 && forced_variant != 4)
     return 0; /* row-band kernels exist for the geometries this policy picks (render_inst.hip: HAS_SPLIT) */
@@ -984,8 +970,8 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
   if (rpp_max > max_rows)
     rpp_max = max_rows;
   int rpp;
-  if (split_request > 0) {
-    rpp = split_request;
+  if (F->split_request > 0) {
+    rpp = F->split_request;
   } else { /* about one band per CU and never more bands than CUs unless the chunk size forces it: a launch of 288 bands
             * takes two turns on 256 CUs (24 half-block frames: 17.0 us in twelve bands each against 9.5 in eight) */
     const int want = n_cus / n_frames > 1 ? n_cus / n_frames : 1;
@@ -1004,7 +990,7 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
      * otherwise the geometry whose chunk matches the band, several of which share a CU */
     const long blocks = (long)n_frames * np;
     const int cells = rpp * max_wp;
-    if (hb || blocks <= n_cus)
+    if (F->hb || blocks <= n_cus)
       *variant = 4;
     else if (cells > variant_caps[2])
       *variant = 1;
@@ -1014,6 +1000,34 @@ int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, b
   *parts = np;
   *rows_per_part = rpp;
   return 0;
+}
+
+int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, bool palette_ascii_only,
+                          const int *variant_caps, int n_cus, int split_request, int forced_variant, int *variant,
+                          int *parts, int *rows_per_part) {
+  const launch_facts_t F = launch_facts(mode, frames, n_frames, palette_ascii_only, n_cus, split_request);
+  *parts = 1;
+  *rows_per_part = F.max_rows > 0 ? F.max_rows : 1;
+  /* Whole-frame geometries (measured on MI355X, profiles/r01_split_sweep.txt, r01_overlap.txt): up to ~1.5
+   * workgroups per CU the 1024-thread x 2-cell geometry (4) has the shortest per-frame latency chain; with more
+   * frames than that in flight -- one large launch, or several launches kept in flight on separate streams, in which
+   * case the caller passes its share of the CUs -- two or three 512-thread workgroups per CU overlap each other's
+   * gather (HBM-bound) and token (latency-bound) phases instead.  Not the half-block modes: their kernels need more
+   * than 128 VGPRs in the small geometries and lose more than the overlap gains. */
+  if (forced_variant >= 0) {
+    if (!forced_applies(&F, variant_caps, forced_variant))
+      return -1;
+    if (forced_variant >= ACHIP_VARIANT_COUNT) {
+      *variant = forced_variant;
+      return 0; /* whole frames only */
+    }
+  } else if (stream_choice(&F, variant_caps, variant, parts) || rows_choice(&F, variant_caps, variant, parts)) {
+    /* automatic: whenever whole frames are launched anyway (the split policy decides that first) */
+    if (*parts > 1)
+      *rows_per_part = 1;
+    return 0;
+  }
+  return phase_choice(&F, variant_caps, forced_variant, variant, parts, rows_per_part);
 }
 
 int achip_frame_blob_parse(const void *blob, size_t size, bool exact, uint32_t *width, uint32_t *height,

@@ -211,7 +211,8 @@ struct asciichat_hip_plan {
   int parts, rows_per_part, split_request; /* multi-workgroup frames (achip_choose_geometry) */
   int whole_variant; /* the geometry of the wire-stage entry points (frame checksums, exact-length frames: a frame belongs to ONE
                         workgroup there): `variant`, unless that shares frames out over workgroups of the stream kernel */
-  long max_cells;                          /* cells of the largest frame (ACHIP_UNIFORM_MAX_CELLS)  */
+  long max_cells;       /* ACHIP_UNIFORM_MAX_CELLS of `variant` (achip_uniform_extent)       */
+  long whole_max_cells; /* ... and of `whole_variant`, for the launches that render whole frames */
   int palette_ascii;
   unsigned long long *part_sync; /* n * parts_cap u64 hand-off words, zeroed once */
   int parts_cap;
@@ -287,6 +288,7 @@ static int choose_geometry(asciichat_hip_plan_t *p, const achip_frame_t *frames)
       return -1;
     p->whole_variant = wv;
   }
+  p->whole_max_cells = achip_uniform_extent(p->mode, p->whole_variant, frames, p->n);
   return 0;
 }
 
@@ -522,12 +524,13 @@ static int render_range_as(asciichat_hip_plan_t *p, int first, int count, uint8_
   achip_uniform_t uni = p->uniform;
   if (p->uniform_off)
     uni.enabled = 0;
-  uni.flags = (p->palette_ascii ? ACHIP_UNIFORM_PALETTE_ASCII : 0u) | ACHIP_UNIFORM_MAX_CELLS(p->max_cells);
   uni.f.src = uni.f.src ? uni.f.src + (int64_t)first * uni.src_pitch : NULL;
   const int shared_out = p->parts > 1 && variant_shares_out(p->variant);
   if (whole && p->parts > 1 && !shared_out)
     return achip_fail(ASCIICHAT_HIP_ERR_NOT_SUPPORTED, "this plan renders row bands");
   const int variant = whole && shared_out ? p->whole_variant : p->variant, parts = whole ? 1 : p->parts;
+  uni.flags = (p->palette_ascii ? ACHIP_UNIFORM_PALETTE_ASCII : 0u) |
+              ACHIP_UNIFORM_MAX_CELLS(whole && shared_out ? p->whole_max_cells : p->max_cells);
   return achip_hip_check(achip_launch_render(p->mode, variant, p->has_comp, p->frames_dev + first, count, p->lut_dev,
                                              out_dev, (uint64_t)out_stride, out_len_dev, phase_cycles_dev, parts,
                                              p->rows_per_part,
@@ -578,7 +581,7 @@ static int plan_render_wire(asciichat_hip_plan_t *p, uint8_t *out_dev, size_t ou
     achip_uniform_t uni = p->uniform;
     if (p->uniform_off)
       uni.enabled = 0;
-    uni.flags = (p->palette_ascii ? ACHIP_UNIFORM_PALETTE_ASCII : 0u) | ACHIP_UNIFORM_MAX_CELLS(p->max_cells);
+    uni.flags = (p->palette_ascii ? ACHIP_UNIFORM_PALETTE_ASCII : 0u) | ACHIP_UNIFORM_MAX_CELLS(p->whole_max_cells);
     return achip_hip_check(achip_launch_render_crc(p->mode, p->whole_variant, p->has_comp, p->frames_dev, p->n, p->lut_dev, out_dev,
                                                    (uint64_t)out_stride, out_len_dev, wire, &uni, prof, stream),
                            "render + crc kernel launch");

@@ -36,6 +36,7 @@
 #pragma once
 
 #include "render_kernels.hpp"
+#include "render_variants.h" /* ACHIP_STREAM_MAXBLK */
 #include "crc_math.hpp" /* the GF(2) toolbox of the wire stage: the frame CRC can ride the drain */
 
 namespace achip {
@@ -58,7 +59,6 @@ __host__ __device__ constexpr int stream_max_token(int m) {
                                  : 48;   /* background: 19 + 19 + 4 + 4 + 1 (rounded up)                         */
 }
 
-#define ACHIP_STREAM_MAXBLK 2048            /* blocks per frame the look-back table holds              */
 #define ACHIP_STREAM_MAX_STRIDE 0x3F000000u /* block prefixes are 30-bit: slab slots up to ~1 GB        */
 
 /* PACK instantiations (frames written at their exact length, below): the whole frame is staged in LDS -- this many bytes

@@ -12,7 +12,6 @@
 #include "render_variants.h"
 
 enum { MOCK_OK = 0, MOCK_INVALID = 1, MOCK_UNSUPPORTED = 801 };
-#define ACHIP_STREAM_MAXBLK 2048 /* render_stream.hpp (a C++ header) */
 
 static uint32_t sample_hash(const achip_frame_t *f) {
   uint32_t h = 2166136261u;
