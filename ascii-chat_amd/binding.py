@@ -357,6 +357,99 @@ def _bind(L):
     return L
 
 
+class RainColumn(C.Structure):  # digital_rain_column_t
+    _fields_ = [("time_offset", C.c_float), ("speed_multiplier", C.c_float), ("phase_offset", C.c_float)]
+
+
+class RainState(C.Structure):  # digital_rain_t (the reference's layout: 56 bytes)
+    _fields_ = [("columns", C.POINTER(RainColumn)), ("num_columns", C.c_int), ("num_rows", C.c_int), ("time", C.c_float),
+                ("fall_speed", C.c_float), ("raindrop_length", C.c_float), ("brightness_decay", C.c_float),
+                ("animation_speed", C.c_float), ("color_r", C.c_uint8), ("color_g", C.c_uint8), ("color_b", C.c_uint8),
+                ("cursor_brightness", C.c_float), ("rainbow_mode", C.c_bool), ("first_frame", C.c_bool),
+                ("previous_brightness", C.POINTER(C.c_float))]
+
+
+def _bind_rain(L):
+    vp = C.c_void_p
+    if getattr(L, "_rain_bound", False):
+        return L
+    P = C.POINTER(RainState)
+    for name, res, args in (("digital_rain_init", P, [C.c_int, C.c_int]), ("digital_rain_destroy", None, [P]),
+                            ("digital_rain_apply", vp, [P, C.c_char_p, C.c_float]), ("digital_rain_reset", None, [P]),
+                            ("digital_rain_set_fall_speed", None, [P, C.c_float]),
+                            ("digital_rain_set_raindrop_length", None, [P, C.c_float]),
+                            ("digital_rain_set_color", None, [P, C.c_uint8, C.c_uint8, C.c_uint8]),
+                            ("digital_rain_set_color_from_filter", None, [P, C.c_int]),
+                            ("asciichat_hip_rain_apply_batch", C.c_int,
+                             [vp, vp, C.c_int, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp]),
+                            ("asciichat_hip_rain_out_stride", C.c_size_t, [C.c_size_t, C.c_size_t]),
+                            ("asciichat_hip_rain_state_dev", vp, [P])):
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    L._rain_bound = True
+    return L
+
+
+class Rain:
+    """A digital rain context (digital_rain_init): .s is the digital_rain_t itself (fields may be written directly),
+    apply() the drop-in digital_rain_apply, apply_batch() the slab form over several contexts."""
+
+    def __init__(self, num_columns, num_rows):
+        self.L = _bind_rain(lib())
+        self.p = self.L.digital_rain_init(num_columns, num_rows)
+        if not self.p:
+            raise RuntimeError(f"digital_rain_init({num_columns}, {num_rows}) failed: {last_error()}")
+        self.s = self.p.contents
+
+    def apply(self, frame, dt):
+        ptr = self.L.digital_rain_apply(self.p, frame, C.c_float(dt))
+        if not ptr:
+            raise RuntimeError(f"digital_rain_apply failed: {last_error()}")
+        return take_string(ptr)
+
+    def reset(self):
+        self.L.digital_rain_reset(self.p)
+
+    def set_fall_speed(self, v):
+        self.L.digital_rain_set_fall_speed(self.p, C.c_float(v))
+
+    def set_raindrop_length(self, v):
+        self.L.digital_rain_set_raindrop_length(self.p, C.c_float(v))
+
+    def set_color(self, r, g, b):
+        self.L.digital_rain_set_color(self.p, r, g, b)
+
+    def set_color_from_filter(self, f):
+        self.L.digital_rain_set_color_from_filter(self.p, f)
+
+    def grid(self):
+        """previous_brightness as the last drop-in apply left it"""
+        return [self.s.previous_brightness[i] for i in range(self.s.num_columns * self.s.num_rows)]
+
+    def state_dev(self):
+        return self.L.asciichat_hip_rain_state_dev(self.p)
+
+    @staticmethod
+    def out_stride(src_stride, max_chars):
+        return _bind_rain(lib()).asciichat_hip_rain_out_stride(src_stride, max_chars)
+
+    @staticmethod
+    def apply_batch(rains, dts, src_ptr, src_stride, src_len_ptr, dst_ptr, dst_stride, dst_len_ptr, stream=0):
+        """asciichat_hip_rain_apply_batch; returns its status (0 = launched)"""
+        L = _bind_rain(lib())
+        n = len(rains)
+        arr = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in rains])
+        dt = (C.c_float * n)(*dts)
+        return L.asciichat_hip_rain_apply_batch(arr, dt, n, src_ptr, src_stride, src_len_ptr, dst_ptr, dst_stride, dst_len_ptr,
+                                                stream)
+
+    def close(self):
+        if self.p:
+            self.L.digital_rain_destroy(self.p)
+            self.p = None
+
+
 def last_error():
     return lib().asciichat_hip_last_error().decode("utf-8", "replace")
 

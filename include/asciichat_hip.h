@@ -296,6 +296,26 @@ int asciichat_hip_pack_frames(const uint8_t *slab_dev, size_t stride, const uint
 int asciichat_hip_plan_render_packed(asciichat_hip_plan_t *plan, uint8_t *slab_dev, size_t out_stride,
                                      uint32_t *out_len_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                      uint32_t *len_out, void *stream);
+
+/*
+ * Digital rain (digital_rain_apply, lib/video/anim/digital_rain.c) over a slab: frame i of src (src_dev + i*src_stride,
+ * src_len_dev[i] bytes, up to its first NUL) through context rains[i] after dt[i] seconds, to dst_dev + i*dst_stride with
+ * its length in dst_len_dev[i] and a NUL behind it; ACHIP_LEN_OVERFLOW when the frame and its NUL do not fit the slot (that
+ * context's brightness grid is then left as it was; nothing is stored beyond a slot).  A length that is an error code
+ * (>= 0xFFFFFFF0) travels on unchanged.  The output is a slab as plan_render leaves one: pack_frames / frame_packets take it
+ * as it is.  Asynchronous: the contexts' time, rainbow colour and first_frame advance when the call is issued; a context's
+ * frames run after its earlier ones, on whatever stream.  A context may appear once per call (else nothing is launched:
+ * ASCIICHAT_HIP_ERR_INVALID_PARAM).  rain_out_stride: a slot size (multiple of 128) that holds any frame of
+ * src_stride bytes and at most max_chars_per_frame characters: len + 19 * chars + 1 (colour SGRs with empty digit runs,
+ * which no renderer emits, can grow by 3 bytes each).  rain_state_dev: the context's device brightness grid
+ * (num_rows x num_columns floats, row-major), created on the current device if it does not exist yet.
+ */
+typedef struct digital_rain digital_rain_t;
+int asciichat_hip_rain_apply_batch(digital_rain_t *const *rains, const float *dt, int n, const uint8_t *src_dev, size_t src_stride,
+                                   const uint32_t *src_len_dev, uint8_t *dst_dev, size_t dst_stride, uint32_t *dst_len_dev,
+                                   void *stream);
+size_t asciichat_hip_rain_out_stride(size_t src_stride, size_t max_chars_per_frame);
+float *asciichat_hip_rain_state_dev(digital_rain_t *rain);
 int asciichat_hip_host_alloc(size_t bytes, void **host_ptr, void **device_alias);
 void asciichat_hip_host_free(void *host_ptr);
 

@@ -244,6 +244,42 @@ size_t frame_get_valid_end(const char *frame_data, size_t frame_size);
 void color_filter_calculate_rainbow(float time, uint8_t *r, uint8_t *g, uint8_t *b);
 char *rainbow_replace_ansi_colors(const char *ansi_string, float time_seconds);
 
+/* ---- video/anim/digital_rain.h:59-93 (types), 162-251 (functions): the --matrix digital rain of the display path
+ * (src/common/session/display.c, src/web/mirror.c:233 reads num_columns / num_rows).  The reference's layout exactly
+ * (56 / 12 bytes); the library keeps its device state in a private tail behind the struct, so contexts come only from
+ * digital_rain_init.  digital_rain_apply runs on the GPU (asciichat_hip_rain_apply_batch is the batch form) and refreshes
+ * previous_brightness from the device before it returns; columns[] are read once, at the context's first apply. */
+typedef struct {
+  float time_offset;
+  float speed_multiplier;
+  float phase_offset; /* stored, never used (as in the reference) */
+} digital_rain_column_t;
+typedef struct digital_rain {
+  digital_rain_column_t *columns;
+  int num_columns;
+  int num_rows;
+  float time;
+  float fall_speed;
+  float raindrop_length;
+  float brightness_decay;
+  float animation_speed;
+  uint8_t color_r;
+  uint8_t color_g;
+  uint8_t color_b;
+  float cursor_brightness; /* stored, never used (as in the reference) */
+  bool rainbow_mode;
+  bool first_frame;
+  float *previous_brightness;
+} digital_rain_t;
+digital_rain_t *digital_rain_init(int num_columns, int num_rows);                 /* digital_rain.h:162 */
+void digital_rain_destroy(digital_rain_t *rain);                                  /* digital_rain.h:171 */
+char *digital_rain_apply(digital_rain_t *rain, const char *frame, float delta_time); /* digital_rain.h:204 */
+void digital_rain_reset(digital_rain_t *rain);                                    /* digital_rain.h:214 */
+void digital_rain_set_fall_speed(digital_rain_t *rain, float speed);              /* digital_rain.h:225 */
+void digital_rain_set_raindrop_length(digital_rain_t *rain, float length);        /* digital_rain.h:232 */
+void digital_rain_set_color(digital_rain_t *rain, uint8_t r, uint8_t g, uint8_t b); /* digital_rain.h:241 */
+void digital_rain_set_color_from_filter(digital_rain_t *rain, color_filter_t filter); /* digital_rain.h:251 */
+
 /* ---- util/aspect_ratio.h ---------------------------------------------------------------------------- */
 void aspect_ratio(const ssize_t img_w, const ssize_t img_h, const ssize_t width, const ssize_t height,
                   const bool stretch, ssize_t *out_width, ssize_t *out_height);

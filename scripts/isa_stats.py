@@ -10,6 +10,7 @@ Extracts the device code objects from the built library, reads every kernel's AM
     has stopped being cheap;
   * render_stream_kernel: <= 64 VGPRs (two 1024-thread or four 512-thread workgroups per CU; the truecolor-background
     mode, whose 48-byte tokens fill the LDS first, <= 72) and no scratch memory (SGPRs parked in VGPR lanes are fine);
+  * rain_kernel: <= 256 VGPRs (two 4-wave workgroups per CU, what its LDS allows) and no scratch;
   * every other kernel: no VGPR spills.
 
 Usage: isa_stats.py [path/to/libasciichat_hip.so] [--out profiles/isa_stats.txt]   (exit status 1 on a violation)
@@ -133,6 +134,9 @@ def main():
                 # (mode 17 = truecolor foreground with multi-byte glyphs, ACHIP_STREAM_MODE_TRUE_FG_U8: its RLE-state chain next
                 # to the tokens; 4 = truecolor background)
                 limit, why = (72, "7 waves per SIMD") if mode in (4, 17) else (64, "8 waves per SIMD")
+        elif "rain_kernel" in name:  # one 4-wave workgroup per frame with up to 57 KB of LDS: two per CU at most
+            short = "achip::rain::rain_kernel"
+            limit, why = 256, "2 waves per SIMD: the two workgroups per CU its LDS allows"
         else:
             short = demangle(name).split("(")[0].replace("void ", "")[-70:]
         problems = []
