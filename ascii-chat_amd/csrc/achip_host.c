@@ -519,6 +519,15 @@ bool achip_frame_extent_ok(const achip_frame_t *f) {
   return extent < 0xFFFFFFF0ull && stride < (1ull << 24);
 }
 
+/* The kernels compute a sample's column as (x * x_ratio) >> 16 in 32 bits (the reference's own arithmetic, image.c:315):
+ * a descriptor whose last column or row would wrap that product is refused on the host, so that every kernel form samples
+ * exactly what the rule in achip_types.h says.  Descriptors of sources of at most 10 000 pixels never come near it. */
+bool achip_frame_ratios_ok(const achip_frame_t *f) {
+  if (!f || f->out_w <= 0 || f->out_h <= 0)
+    return false;
+  return (uint64_t)(f->out_w - 1) * f->x_ratio < (1ull << 32) && (uint64_t)(f->out_h - 1) * f->y_ratio < (1ull << 32);
+}
+
 /* cells ((pad_left + out_w) * out_h) of the largest frame: what ACHIP_UNIFORM_MAX_CELLS carries to the stream kernel */
 long achip_max_cells(const achip_frame_t *frames, int n_frames) {
   long max_cells = 0;

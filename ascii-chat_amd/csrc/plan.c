@@ -316,6 +316,10 @@ static int plan_measure(asciichat_hip_plan_t *p, const achip_frame_t *frames) {
     if (!achip_frame_extent_ok(f))
       return achip_fail(ASCIICHAT_HIP_ERR_INVALID_PARAM, "frame %d: source spans 4 GiB or more (row stride %d)", i,
                         f->src_stride);
+    if (!achip_frame_ratios_ok(f))
+      return achip_fail(ASCIICHAT_HIP_ERR_INVALID_PARAM,
+                        "frame %d: (out_w - 1) * x_ratio or (out_h - 1) * y_ratio reaches 2^32 (out %dx%d, ratios %u / %u)", i,
+                        f->out_w, f->out_h, f->x_ratio, f->y_ratio);
     size_t b = achip_out_bound(q.mode, f) + 1;
     if (b > stride)
       stride = b;
@@ -456,6 +460,10 @@ int asciichat_hip_plan_set_variant(asciichat_hip_plan_t *p, int variant) {
     return ASCIICHAT_HIP_ERR_INVALID_PARAM;
   if (variant >= 0 && achip_variant_block(variant) <= 0)
     return achip_fail(ASCIICHAT_HIP_ERR_NOT_SUPPORTED, "geometry %d is not in this build (render_variants.h: make EXTRA=-DACHIP_ALL_GEOMETRIES)", variant);
+  if (variant >= 0 && ACHIP_IS_ROWS_VARIANT(variant) && ACHIP_ROWS_VARIANT_PARTS(variant)) /* (a forced geometry renders whole
+    frames: these kernels always share a frame out and publish to hand-off words that only an automatic choice allocates) */
+    return achip_fail(ASCIICHAT_HIP_ERR_NOT_SUPPORTED, "geometry %d shares frames out over workgroups: plans take it by themselves",
+                      variant);
   if (variant >= 0 && !ACHIP_IS_STREAM_VARIANT(variant) && achip_variant_cap(variant) < p->max_wp) /* (a stream geometry's
                                                              "cap" is cells per frame: plan_measure judges those) */
     return achip_fail(ASCIICHAT_HIP_ERR_NOT_SUPPORTED, "variant %d cannot hold a %d-cell row", variant, p->max_wp);

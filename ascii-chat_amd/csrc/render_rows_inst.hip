@@ -113,7 +113,8 @@ extern "C" int ACHIP_CAT(ACHIP_CAT(ACHIP_CAT(achipk_render_rinst_launch_, ACHIP_
   achip_partsdev_t ps = {1, 1u, nullptr};
   if (parts)
     ps = *parts;
-  if (ps.parts < 1 || ps.parts > 64 || (ps.parts > 1 && (!G::PARTS || !ps.sync || ps.epoch == 0u)))
+  if (ps.parts < 1 || ps.parts > 64 || (ps.parts > 1 && (!G::PARTS || !ps.sync || ps.epoch == 0u)) ||
+      (G::PARTS && (!ps.sync || ps.epoch == 0u))) /* (a PARTS kernel publishes to ps.sync even as one part) */
     return (int)hipErrorInvalidValue;
   achip_uniform_t uni = {};
   if (uniform && uniform->enabled) /* (composite batches too: achip_frames_uniform) */

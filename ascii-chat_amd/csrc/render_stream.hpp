@@ -628,7 +628,7 @@ __global__ void __launch_bounds__(WAVES * 64)
         if (wire.pkt_crc)
           wire.pkt_crc[fidx] = ~crc_mulmod(0xFFFFFFFFu, crc_pow(CRC_X8, 24u));
       }
-      if (PACK)
+      if (PACK || LF) /* every workgroup of a launch on the cursor reports in, a refused frame too */
         pack_report(agent_fetch_add_u64(&pack.cursor[0], 0ull), ACHIP_LEN_BADDESC);
     }
     return;
@@ -719,7 +719,8 @@ __global__ void __launch_bounds__(WAVES * 64)
    * cell c0 + 64 j: there the lanes of ONE load instruction fetch neighbouring cells, and neighbours that share a line
    * (1080p -> 80 columns: 72 bytes apart) are one request; lane-major they are two requests of two instructions, and
    * the metric's launch, bound by requests, takes 9.97 instead of 6.89 us (profiles/r06_stream_lean_ab.txt, visit A). */
-  const bool lean_dense = f.x_ratio == 65537u && f.y_ratio == 65537u; /* (x * 65537) >> 16 = x for x < 65536 */
+  /* (x * 65537) >> 16 = x for x < 65536; the sample is x itself only where the clamp to src_w - 1 can not bite */
+  const bool lean_dense = f.x_ratio == 65537u && f.y_ratio == 65537u && f.src_w == f.out_w && f.src_h == f.out_h;
   const uint32_t xr_lo = f.x_ratio & 0xFFFFu, xr_hi = f.x_ratio >> 16, yr_lo = f.y_ratio & 0xFFFFu, yr_hi = f.y_ratio >> 16;
   const int32_t lean_mx = src.flip_x ? -3 : 3;
   const uint32_t lean_ax = src.flip_x ? 3u * src.w1 : 0u;
@@ -798,7 +799,7 @@ __global__ void __launch_bounds__(WAVES * 64)
   if (RMODE == ACHIP_MODE_TRUE_FG && ascii_only == U8) { /* (the launchers pick the instantiation by the palette) */
     if (tid == 0) {
       out_len[fidx] = ACHIP_LEN_BADDESC;
-      if (PACK)
+      if (PACK || LF)
         pack_report(agent_fetch_add_u64(&pack.cursor[0], 0ull), ACHIP_LEN_BADDESC);
     }
     return;

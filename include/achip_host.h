@@ -94,6 +94,8 @@ long achip_max_cells(const achip_frame_t *frames, int n_frames);
 long achip_uniform_extent(int mode, int variant, const achip_frame_t *frames, int n_frames);
 /* false for a descriptor the kernels' 32-bit source offsets (and 24-bit row-stride multiply) cannot address */
 bool achip_frame_extent_ok(const achip_frame_t *f);
+/* false when (out_w - 1) * x_ratio or (out_h - 1) * y_ratio reaches 2^32 (the kernels' 32-bit sample index would wrap) */
+bool achip_frame_ratios_ok(const achip_frame_t *f);
 int achip_choose_geometry(int mode, const achip_frame_t *frames, int n_frames, bool palette_ascii_only,
                           const int *variant_caps, int n_cus, int split_request, int forced_variant, int *variant,
                           int *parts, int *rows_per_part);

@@ -49,7 +49,10 @@ typedef struct {
 } achip_composite_t;
 
 /* One frame of a batch.  Sampling is the reference's nearest-neighbour rule (image.c:293-325):
- * sx = min((x * x_ratio) >> 16, src_w - 1). */
+ * sx = min((x * x_ratio) >> 16, src_w - 1), sy = min((y * y_ratio) >> 16, src_h - 1), then the flips of `ops`
+ * (sx -> src_w - 1 - sx, sy -> src_h - 1 - sy); pixel (sx, sy) is at src + sy * src_stride + 3 * sx.  Plans refuse a
+ * descriptor whose products wrap 32 bits: (out_w - 1) * x_ratio and (out_h - 1) * y_ratio must stay below 2^32
+ * (achip_frame_ratios_ok). */
 typedef struct {
   const uint8_t *src;            /* RGB24 source frame (device-visible); ignored when comp != NULL */
   const achip_composite_t *comp; /* optional: sample a virtual composite canvas instead of src     */

@@ -208,6 +208,29 @@ def render_frames_packed(mode, frames, palette, variant=16, stride=None, dims=No
     return dict(lens=ln, off=off, plen=plen, dst=view, crc=crc, hdr=hdr, pkt=pkt, cursor=cur, stride=stride)
 
 
+def check_packed(res, expected, what):
+    """frames at their exact lengths, 16-byte aligned starts, tiling [0, total) in SOME order; error frames take no room"""
+    n = len(expected)
+    spans = []
+    for k, exp in enumerate(expected):
+        o = int(res["off"][k])
+        if isinstance(exp, int):  # a render error code
+            assert int(res["plen"][k]) == exp and int(res["lens"][k]) == exp, (what, k)
+            continue
+        assert int(res["plen"][k]) == len(exp) == int(res["lens"][k]), (what, k, int(res["plen"][k]), len(exp))
+        assert o % 16 == 0 and res["dst"][o:o + len(exp)].tobytes() == exp, (what, k)
+        room = (len(exp) + 15) // 16 * 16
+        assert not res["dst"][o + len(exp):o + room].any(), (what, k)  # the padding leaves as zeros
+        spans.append((o, o + room))
+    spans.sort()
+    at = 0
+    for a, b in spans:
+        assert a == at, (what, spans)
+        at = b
+    assert int(res["off"][n]) == at, (what, int(res["off"][n]), at)
+    assert not res["cursor"].any(), what  # re-armed for the plan's next launch
+
+
 def render_frames_length_first(frames, palette, variant=17, stride=None, capacity=None, cursor=None, uniform=False):
     """The stream kernel's LENGTH-FIRST instantiation (exact-length truecolor-foreground frames of any size in one launch):
     dict(lens, off, plen, dst, cursor, stride) as render_frames_packed."""

@@ -95,7 +95,16 @@ static int by_mode(int mode, const achip_frame_t *frames, int n, const achip_lut
 /* As the product's launchers: the fast-sampler instantiation (GENERIC = false) unless a frame needs the full repertoire --
  * a virtual composite or a 1x1 source.  (Until round 5 this driver always took GENERIC = true: the fast sampler, and with it
  * the rows kernel's scalar-row path, ran on the GPU only.) */
+static int g_fast_only = 0; /* 1: never pick the general sampler here, so that the fast-sampler kernels' own checks refuse
+                               the frames it would have taken (tests of a kernel's refusal contract) */
+extern "C" int emu_set_fast_sampler_only(int on) {
+  const int was = g_fast_only;
+  g_fast_only = on;
+  return was;
+}
 static bool needs_generic(const achip_frame_t *frames, int n) {
+  if (g_fast_only)
+    return false;
   for (int i = 0; i < n; i++)
     if (frames[i].comp || frames[i].src_w * frames[i].src_h == 1)
       return true;

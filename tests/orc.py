@@ -247,6 +247,16 @@ def display_convert(img, width, height, color_level, render_mode, wants_padding=
     return _take(p, n.value)
 
 
+def pad_width(frame, pad_left):
+    """ascii_pad_frame_width: pad_left spaces in front of every line"""
+    return _take(lib().orc_pad_width(bytes(frame), pad_left))
+
+
+def pad_height(frame, pad_top):
+    """ascii_pad_frame_height: pad_top newlines in front of the frame"""
+    return _take(lib().orc_pad_height(bytes(frame), pad_top))
+
+
 def color_filter(img, flt):
     out = _img(img).copy()
     assert lib().orc_color_filter(out.ctypes.data, out.shape[1], out.shape[0], out.shape[1] * 3, flt) == 0

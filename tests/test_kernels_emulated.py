@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import emu
+from emu import check_packed
 import orc
 from achip_ctypes import (ALL_MODES, MODE_16_FG, MODE_256_FG, MODE_CAPS, MODE_HB_TRUE, MODE_MONO, MODE_NAMES,
                           MODE_TRUE_BG, MODE_TRUE_FG)
@@ -479,29 +480,6 @@ def test_stream_kernel_fused_frame_crc(mode):
         assert got[0] == oracle_convert(TORTURE, mode, 61, 17, "é漢😀 .") and crc[0] == orc.crc32c(got[0])
     got, crc = emu.render_frames_crc(mode, [frames[0]], orc.PALETTE_STANDARD, 20, stride=1024)
     assert got[0] == 0xFFFFFFFF and crc[0] == 0
-
-
-def check_packed(res, expected, what):
-    """frames at their exact lengths, 16-byte aligned starts, tiling [0, total) in SOME order; error frames take no room"""
-    n = len(expected)
-    spans = []
-    for k, exp in enumerate(expected):
-        o = int(res["off"][k])
-        if isinstance(exp, int):  # a render error code
-            assert int(res["plen"][k]) == exp and int(res["lens"][k]) == exp, (what, k)
-            continue
-        assert int(res["plen"][k]) == len(exp) == int(res["lens"][k]), (what, k, int(res["plen"][k]), len(exp))
-        assert o % 16 == 0 and res["dst"][o:o + len(exp)].tobytes() == exp, (what, k)
-        room = (len(exp) + 15) // 16 * 16
-        assert not res["dst"][o + len(exp):o + room].any(), (what, k)  # the padding leaves as zeros
-        spans.append((o, o + room))
-    spans.sort()
-    at = 0
-    for a, b in spans:
-        assert a == at, (what, spans)
-        at = b
-    assert int(res["off"][n]) == at, (what, int(res["off"][n]), at)
-    assert not res["cursor"].any(), what  # re-armed for the plan's next launch
 
 
 @pytest.mark.parametrize("mode", [MODE_TRUE_FG, MODE_256_FG, 3], ids=["true_fg", "256_fg", "16_fg"])
