@@ -18,14 +18,19 @@ Protocol (VERDICT r1 "next round" 1-2):
     (`--regions R` repeats the region R times and takes the MEDIAN region, for profiling runs);
   * a fresh input batch every step (12 batches rotate: no step re-reads the previous step's frames out of the 256 MB
     Infinity Cache);
-  * `roofline.kernel_ms` = GPU time per step from HIP events recorded on the launch streams around a long
-    back-to-back run of the same schedule; `roofline.achieved` = algorithmic bytes per launch / kernel_ms;
-  * after timing, 8 frames per workload are compared byte-for-byte with the CPU oracle on the very same input frames;
   * everything in the line was measured by this run, except what sits under "committed_profile" (rocprofv3 summaries
     from profiles/, labelled with their source).
 
-Prints ONE compact JSON line on rank 0 (< 4 KB: the contract's keys + roofline + cpu_baseline + verify + a digest of the
-other workloads); the full record of the run -- every leg, table and note -- goes to the side file `--extra`
+A plain run does only what the headline needs: it sets up, calibrates S, warms up, times the steps, writes
+`--dump-outputs` if asked and prints the line.  `--full` adds everything else this file measures or checks:
+  * `roofline.kernel_ms` = GPU time per step from HIP events recorded on the launch streams around a long
+    back-to-back run of the same schedule; `roofline.achieved` = algorithmic bytes per launch / kernel_ms;
+  * after timing, 8 frames per workload are compared byte-for-byte with the CPU oracle on the very same input frames;
+  * one launch at a time, the PCIe-inclusive, wire-stage and server-tick legs, the CPU baseline, the other workloads
+    (`--others`), the batch-size axis (`--batch-sweep`) and, for N > 1, the all-gather of the rendered frames.
+
+Prints ONE compact JSON line on rank 0 (< 4 KB: the contract's keys, with --full also roofline + cpu_baseline + verify + a
+digest of the other workloads); the full record of the run -- every leg, table and note -- goes to the side file `--extra`
 (default bench_extra.json next to this script).
 """
 import argparse
@@ -230,7 +235,11 @@ def verify_against_oracle(torch, pkg, plan, frames_t, W, H, cl, rm, aspect, n_ch
 
 
 def run_workload(torch, pkg, name, batch, steps, warmup, regions, dist=None, seed=1234, variant=-1, nsets=12,
-                 streams=4, kind="noise", aspect=False, serial_leg=True, verify=True, streams_auto=None, keep_last=False):
+                 streams=4, kind="noise", aspect=False, serial_leg=True, verify=True, streams_auto=None, keep_last=False,
+                 roofline=True):
+    """Sets up, calibrates the launches in flight (streams_auto), warms up and times `regions` regions of `steps` steps.
+    verify, roofline and serial_leg add the legs of a --full run: the oracle comparison, the passes the roofline needs
+    (exact output bytes of every input set, HIP-event kernel time) and the one-launch-at-a-time leg."""
     sw, sh, W, H, cl, rm = WORKLOADS[name]
     assert nsets % streams == 0 and all(nsets % c == 0 for c in (streams_auto or ()))
     sets = [make_frames(torch, batch, sw, sh, seed + 7919 * s, kind) for s in range(nsets)]
@@ -266,7 +275,7 @@ def run_workload(torch, pkg, name, batch, steps, warmup, regions, dist=None, see
                  else (None, None))
     # exact output bytes of every input set (B_alg = sampled RGB consumed + exact output length)
     out_bytes = []
-    for g in range(0, nsets, streams):
+    for g in range(0, nsets, streams) if roofline else ():
         run.step = g
         run.issue(streams)
         torch.cuda.synchronize()
@@ -283,13 +292,15 @@ def run_workload(torch, pkg, name, batch, steps, warmup, regions, dist=None, see
         k = run.step - 1
         last = {"slab": run.outs[k % streams].cpu().numpy(), "lens": run.lns[k % streams].cpu().numpy().astype("uint32"),
                 "stride": run.stride}
-    gpu_ms = run.gpu_ms_per_step(max(200, steps))
+    gpu_ms = out_mean = alg_bytes = None
     f0 = pkg.frame_setup(sets[0].data_ptr(), sw, sh, W, H, rm, aspect, aspect, False)
-    cells_px = f0.out_w * f0.out_h  # sampled pixels per frame (2 rows per text row in half-block)
-    out_mean = sum(out_bytes) / len(out_bytes)
-    alg_bytes = int(out_mean) + batch * 3 * cells_px
+    if roofline:
+        gpu_ms = run.gpu_ms_per_step(max(200, steps))
+        cells_px = f0.out_w * f0.out_h  # sampled pixels per frame (2 rows per text row in half-block)
+        out_mean = sum(out_bytes) / len(out_bytes)
+        alg_bytes = int(out_mean) + batch * 3 * cells_px
     res = dict(name=name, mode=pkg.MODE_NAMES[mode], batch=batch, walls=walls, steps=steps, gpu_ms=gpu_ms,
-               out_bytes_per_frame=out_mean / batch, alg_bytes_per_launch=alg_bytes, variant=plans[0].variant,
+               out_bytes_per_frame=out_mean / batch if roofline else None, alg_bytes_per_launch=alg_bytes, variant=plans[0].variant,
                input_sets=nsets, streams=streams, kind=kind, aspect=aspect, verify=ver, streams_autotune=tune,
                cells_per_frame=(f0.pad_left + f0.out_w) * ((f0.out_h + 1) // 2 if rm == 2 else f0.out_h),
                serial=None, plans=plans, sets=sets, forced_variant=variant, last=last)
@@ -316,17 +327,20 @@ def run_workload(torch, pkg, name, batch, steps, warmup, regions, dist=None, see
 def summarize(res, world=1, wall=None):
     """Per-workload entry of the JSON line (everything measured by this run)."""
     wall = statistics.median(res["walls"]) if wall is None else wall
-    k = res["gpu_ms"]
-    a = res["alg_bytes_per_launch"] / (k * 1e-3) / 1e9
     fps = res["batch"] * res["steps"] * world / wall
-    d = {"frames_per_s": fps, "ms_per_step": wall / res["steps"] * 1e3, "kernel_ms": k, "launches_in_flight": res["streams"],
+    d = {"frames_per_s": fps, "ms_per_step": wall / res["steps"] * 1e3, "launches_in_flight": res["streams"],
          "region_ms": {"min": min(res["walls"]) * 1e3, "median": statistics.median(res["walls"]) * 1e3,
                        "max": max(res["walls"]) * 1e3, "regions": len(res["walls"]), "steps_per_region": res["steps"]},
          "input": res["kind"], "aspect_and_padding": res["aspect"], "mode": res["mode"],
-         "out_bytes_per_frame": res["out_bytes_per_frame"], "alg_bytes_per_launch": res["alg_bytes_per_launch"],
-         "output_GBps": res["out_bytes_per_frame"] * fps / 1e9, "cells_per_s": res["cells_per_frame"] * fps,
-         "roofline_GBps": a, "roofline_frac": a / HBM_PEAK_GBS, "kernel_variant": res["variant"],
-         "input_sets": res["input_sets"], "verify": res["verify"]}
+         "cells_per_s": res["cells_per_frame"] * fps, "kernel_variant": res["variant"], "input_sets": res["input_sets"]}
+    k = res["gpu_ms"]
+    if k is not None:  # the roofline passes ran
+        a = res["alg_bytes_per_launch"] / (k * 1e-3) / 1e9
+        d.update({"kernel_ms": k, "out_bytes_per_frame": res["out_bytes_per_frame"],
+                  "alg_bytes_per_launch": res["alg_bytes_per_launch"], "output_GBps": res["out_bytes_per_frame"] * fps / 1e9,
+                  "roofline_GBps": a, "roofline_frac": a / HBM_PEAK_GBS})
+    if res["verify"] is not None:
+        d["verify"] = res["verify"]
     if res.get("streams_autotune"):
         d["launches_in_flight_autotune_ms_per_step"] = {str(k): v for k, v in res["streams_autotune"].items()}
     if res["serial"] is not None:
@@ -402,7 +416,7 @@ def time_with_d2h(torch, plan, n, steps):
     return (time.perf_counter() - t0) / steps, int(buf.numel())
 
 
-def run_grid9(torch, pkg, steps, regions, targets=256, dist=None, world=1, rank=0, backend="nccl", last=None):
+def run_grid9(torch, pkg, steps, regions, targets=256, dist=None, world=1, rank=0, backend="nccl", last=None, full=True):
     """BASELINE configs[3]: nine 1080p sources -> the 3x3 grid at 160x48 (stream.c:523-854), sharded over the ranks
     with an RCCL all-gather for the composite -- through the C-ABI (asciichat_hip_comm_* / asciichat_hip_grid_*):
     a step = every rank resizes the sources it owns into their tiles, ONE ncclAllGather moves the tiles to every rank,
@@ -1184,6 +1198,11 @@ def main():
                     help="after the timed steps, write what the last one computed (frame lengths and bytes) as DIR/*.npy")
     ap.add_argument("--no-hot", action="store_true",
                     help="skip the one-launch-at-a-time / same-batch comparison legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: the oracle comparison, the roofline passes "
+                         "and committed profile, the legs above (--others, --batch-sweep, CPU baseline, wire stage, PCIe, "
+                         "one launch at a time) and, for N > 1, the all-gather leg.  Without it a run sets up, warms up, "
+                         "times the steps, writes --dump-outputs and prints the line")
     args = ap.parse_args()
     maybe_spawn_ranks(args)
     # stdout carries ONE line, the JSON: libraries that print to the process's stdout on their own (RCCL's version
@@ -1257,9 +1276,9 @@ def main():
         return
     res = run_workload(torch, pkg, args.workload, args.batch, args.steps, args.warmup, regions, dist, seed=1234 + rank,
                        variant=args.variant, nsets=args.input_sets, streams=args.streams or 4, kind=args.input,
-                       aspect=args.aspect, serial_leg=not args.no_hot,
+                       aspect=args.aspect, serial_leg=args.full and not args.no_hot, verify=args.full,
                        streams_auto=(1, 2, 3, 4) if args.streams == 0 and world == 1 else None,
-                       keep_last=bool(args.dump_outputs))
+                       keep_last=bool(args.dump_outputs), roofline=args.full)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, res.pop("last"), f"rank{rank}_" if world > 1 else "")
     walls = res["walls"]
@@ -1293,33 +1312,37 @@ def main():
                    "parallelism": f"frames sharded over {world} rank(s), no data-path collective",
                    "kernel_variant": res["variant"], "input_sets": res["input_sets"],
                    "launches_in_flight": res["streams"]},
-        "roofline": {"bound": "hbm", "achieved": main_d["roofline_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": main_d["roofline_frac"], "traffic": None,
-                     # the same algorithmic bytes over the TIMED REGIONS' own clock (ms_per_step, what `value` is made of:
-                     # a short region carries the queues' wake-up, so this one is the lower of the two -- VERDICT r5 weak 9)
-                     "frac_timed_region": res["alg_bytes_per_launch"] / (main_d["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "alg_bytes_per_launch": res["alg_bytes_per_launch"], "kernel_ms": res["gpu_ms"],
-                     "launches_in_flight": res["streams"], "out_bytes_per_frame": res["out_bytes_per_frame"],
-                     "kernel_ms_note": "GPU time per step (HIP events on the launch streams, first begin -> last end of a "
-                                       "back-to-back run of the same schedule); with launches overlapping this is what "
-                                       "one launch costs, not one dispatch's begin-to-end duration",
-                     "traffic_note": "HBM bytes need rocprofv3 --pmc passes, which this run did not make: see "
-                                     "committed_profile (if present) for the committed figure and its source"},
-        "output_GBps": main_d["output_GBps"], "cells_per_s": main_d["cells_per_s"], "verify": res["verify"],
+        "cells_per_s": main_d["cells_per_s"],
     }
+    if args.full:
+        line["roofline"] = {
+            "bound": "hbm", "achieved": main_d["roofline_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": main_d["roofline_frac"], "traffic": None,
+            # the same algorithmic bytes over the TIMED REGIONS' own clock (ms_per_step, what `value` is made of:
+            # a short region carries the queues' wake-up, so this one is the lower of the two -- VERDICT r5 weak 9)
+            "frac_timed_region": res["alg_bytes_per_launch"] / (main_d["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "alg_bytes_per_launch": res["alg_bytes_per_launch"], "kernel_ms": res["gpu_ms"],
+            "launches_in_flight": res["streams"], "out_bytes_per_frame": res["out_bytes_per_frame"],
+            "kernel_ms_note": "GPU time per step (HIP events on the launch streams, first begin -> last end of a "
+                              "back-to-back run of the same schedule); with launches overlapping this is what "
+                              "one launch costs, not one dispatch's begin-to-end duration",
+            "traffic_note": "HBM bytes need rocprofv3 --pmc passes, which this run did not make: see "
+                            "committed_profile (if present) for the committed figure and its source"}
+        line["output_GBps"] = main_d["output_GBps"]
+        line["verify"] = res["verify"]
     if res.get("streams_autotune"):
         line["timing"]["launches_in_flight_autotune_ms_per_step"] = {str(k): v for k, v in res["streams_autotune"].items()}
     if res["serial"] is not None:
         line["one_launch_at_a_time"] = res["serial"]
     if multi is not None:
+        line["multi_gpu"] = multi
+        line["rccl_ranks"] = None
+    if multi is not None and args.full:
         # the C-ABI's own communicator over these ranks (comm.c): how many ranks RCCL sees, and what gathering every
         # rank's frames costs -- outside the timed regions (the metric's path has no collective), AFTER the line is
         # complete and under a watchdog: if the optional leg wedges (a rank that cannot join a collective blocks the
         # others inside RCCL, where no exception can reach them) every rank gives up after MULTI_LEG_TIMEOUT_S and rank 0
         # still prints the timing line
-        line["multi_gpu"] = multi
-        line["rccl_ranks"] = None
-
         def give_up():
             multi["error"] = f"the all-gather leg did not finish within {MULTI_LEG_TIMEOUT_S} s; timing line printed without it"
             if rank == 0:
@@ -1340,7 +1363,7 @@ def main():
             multi["error"] = str(e)[:300]
         watchdog.cancel()
         line["rccl_ranks"] = multi.get("rccl_ranks")
-    cp = committed_profile(args.workload)
+    cp = committed_profile(args.workload) if args.full else None
     if cp is not None:
         line["committed_profile"] = cp
         tr = cp.get("traffic") or {}
@@ -1370,7 +1393,7 @@ def main():
             else:
                 line["committed_profile_stale"] = {"profile_source_id": fp.get("source_id"), "tree_source_id": here,
                                                    "note": "the committed traces are of other sources than this tree: no frac_profile"}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_d2h:
             d2h_s, d2h_bytes = time_with_d2h(torch, res["plans"][0], args.batch, 50)
             line["with_d2h"] = {"ms_per_step": d2h_s * 1e3, "frames_per_s": args.batch / d2h_s,

@@ -9,7 +9,7 @@ for w in $WL; do
   for rep in $(seq $REPS); do
     for lib in $LIBS; do
       path=""; [ "$lib" != HEAD ] && path=$PWD/ascii-chat_amd/$lib
-      ASCIICHAT_HIP_LIB=$path timeout 300 python3 bench.py --workload $w --others '' --no-cpu --no-wire --no-d2h $( [ -n "${HOT:-}" ] || echo --no-hot ) --batch-sweep '' --steps 100 --warmup 20 ${INPUT:+--input $INPUT} \
+      ASCIICHAT_HIP_LIB=$path timeout 300 python3 bench.py --full --workload $w --others '' --no-cpu --no-wire --no-d2h $( [ -n "${HOT:-}" ] || echo --no-hot ) --batch-sweep '' --steps 100 --warmup 20 ${INPUT:+--input $INPUT} \
          --extra $O/extra_${w}_${lib}_$rep.json > $O/line_${w}_${lib}_$rep.txt 2>> $O/stderr.txt
       python3 - "$O/extra_${w}_${lib}_$rep.json" "$w" "$lib" <<'PY'
 import json,sys

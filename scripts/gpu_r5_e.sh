@@ -5,7 +5,7 @@
 TAG=${1:-r5e}; O=gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -x > $O/pytest_default.log 2>&1; echo "pytest default build rc=$?" >> $O/pytest_default.log; grep -E "passed|failed|FAILED|rc=" $O/pytest_default.log | tail -6
 ASCIICHAT_HIP_LIB=$PWD/ascii-chat_amd/lib_all.so timeout 1500 python -m pytest tests -m gpu -q -x > $O/pytest_all_geometries.log 2>&1; echo "pytest all-geometries build rc=$?" >> $O/pytest_all_geometries.log; grep -E "passed|failed|FAILED|rc=" $O/pytest_all_geometries.log | tail -6
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_stdout.txt 2> $O/bench_driver_stderr.txt; echo "bench rc=$?"
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_stdout.txt 2> $O/bench_driver_stderr.txt; echo "bench rc=$?"
 cp bench_extra.json $O/bench_extra_driver_flags.json 2>/dev/null
 wc -c $O/bench_driver_stdout.txt; head -c 900 $O/bench_driver_stdout.txt; echo; TAG=$TAG python3 - <<'PY'
 import json, os

@@ -2,7 +2,7 @@
 # the headline's kernel trace, again: rocprofv3's tracer serialises short launches to a box- and run-dependent degree (1.6-2.9 of
 # the four requested stay in flight); scripts/r5_commit_profiles.py takes the run that kept the most.  usage: <tag> [sets]
 TAG=${1:-r5ht}; SETS=${2:-2}; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-COMMON="--warmup 5 --no-cpu --no-d2h --no-hot --no-wire --others none --batch-sweep= --extra ''"
+COMMON="--full --warmup 5 --no-cpu --no-d2h --no-hot --no-wire --others none --batch-sweep= --extra ''"
 for s in $(seq $SETS); do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/${TAG}_$s; mkdir -p $OUT
   for name in headline_s4 headline_s4b headline_s4c; do

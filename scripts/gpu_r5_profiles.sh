@@ -5,7 +5,7 @@
 # Outputs: gpurun_out/<tag>/ -> copied to profiles/r05_* (scripts/r5_commit_profiles.py writes committed_profile.json's round-5 entries).
 TAG=${1:-r5prof}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-COMMON="--warmup 5 --no-cpu --no-d2h --no-hot --no-wire --others none --batch-sweep= --extra ''"
+COMMON="--full --warmup 5 --no-cpu --no-d2h --no-hot --no-wire --others none --batch-sweep= --extra ''"
 reduce() { # name
   local csvf=$(find $OUT/t_$1 -name "*kernel_trace.csv" | head -1)
   if [ -n "$csvf" ]; then python scripts/trace_stats.py $csvf $OUT/${1}_kernel_stats.csv $OUT/${1}_trace_overlap.json > /dev/null; else echo "$1: no trace"; fi

@@ -4,7 +4,7 @@
 TAG=${1:-r6d}; O=gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
 timeout 1200 python -m pytest tests -m gpu -q -x -k "multibyte or palettes or stream or torture" > $O/pytest_u8.log 2>&1; echo "pytest rc=$?" >> $O/pytest_u8.log; tail -4 $O/pytest_u8.log
 leg() { # workload, variant
-  timeout 300 python3 bench.py --workload $1 --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 100 --warmup 20 ${2:+--variant $2} --extra $O/extra_$1_${2:-auto}.json > $O/line_$1_${2:-auto}.txt 2>> $O/stderr.txt
+  timeout 300 python3 bench.py --full --workload $1 --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 100 --warmup 20 ${2:+--variant $2} --extra $O/extra_$1_${2:-auto}.json > $O/line_$1_${2:-auto}.txt 2>> $O/stderr.txt
   python3 - $O/extra_$1_${2:-auto}.json $1 ${2:-auto} <<'PY'
 import json,sys
 try:

@@ -3,7 +3,7 @@
 TAG=${1:-r6e}; O=gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
 leg() { # workload, extra args
   local w=$1; shift
-  timeout 600 python3 bench.py --workload $w --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 20 --warmup 5 --regions 5 --input-sets 4 --streams 4 "$@" --extra $O/extra_$w.json > $O/line_$w.txt 2>> $O/stderr.txt
+  timeout 600 python3 bench.py --full --workload $w --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 20 --warmup 5 --regions 5 --input-sets 4 --streams 4 "$@" --extra $O/extra_$w.json > $O/line_$w.txt 2>> $O/stderr.txt
   python3 - $O/extra_$w.json $w <<'PY'
 import json,sys
 try:

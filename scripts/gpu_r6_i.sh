@@ -5,7 +5,7 @@
 TAG=${1:-r6i}; O=gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -x -k "rows or torture or aspect or full_size" > $O/pytest_rows.log 2>&1; echo "pytest rc=$?" >> $O/pytest_rows.log; tail -4 $O/pytest_rows.log
 leg() { # workload, variant
-  timeout 600 python3 bench.py --workload $1 --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 40 --warmup 10 ${2:+--variant $2} --extra $O/extra_$1_${2:-auto}.json > $O/line_$1_${2:-auto}.txt 2>> $O/stderr.txt
+  timeout 600 python3 bench.py --full --workload $1 --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 40 --warmup 10 ${2:+--variant $2} --extra $O/extra_$1_${2:-auto}.json > $O/line_$1_${2:-auto}.txt 2>> $O/stderr.txt
   python3 - $O/extra_$1_${2:-auto}.json $1 ${2:-auto} <<'PY'
 import json,sys
 try:

@@ -14,7 +14,7 @@ for lib in HEAD lib_p2.so; do
   done
 done > $O/small_parts_sweep.txt; cat $O/small_parts_sweep.txt
 for rep in 1 2 3; do
-timeout 300 python3 bench.py --workload 640x480_80x24_mono --batch 1 --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 100 --warmup 20 --extra $O/extra_k1_$rep.json > $O/line_k1_$rep.txt 2>> $O/stderr.txt
+timeout 300 python3 bench.py --full --workload 640x480_80x24_mono --batch 1 --others '' --no-cpu --no-wire --no-d2h --batch-sweep '' --steps 100 --warmup 20 --extra $O/extra_k1_$rep.json > $O/line_k1_$rep.txt 2>> $O/stderr.txt
 python3 -c "
 import json; d=json.load(open('$O/extra_k1_$rep.json')); r=d['roofline']; print('configs[0] lone mono frame: value', d['value'], d['unit'], 'ms_per_step', d['ms_per_step']*1e3, 'us kernel', r['kernel_ms']*1e3, 'us variant', d['config'].get('kernel_variant'), 'verify', (d.get('verify') or {}).get('byte_identical_to_oracle'))"
 done | tee $O/k1.txt

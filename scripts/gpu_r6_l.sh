@@ -5,7 +5,7 @@ TAG=${1:-r6l}; O=gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -k "small_launches or rows or torture or dropin or graph_replay or split or multi_workgroup or tick or palettes" > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -4 $O/pytest.log
 timeout 900 python3 scripts/gpu_small_run_modes.py 1 8 32 > $O/small_all_forms.txt 2>> $O/stderr.txt; cat $O/small_all_forms.txt | cut -c1-330
 for rep in 1 2; do
-timeout 300 python3 bench.py --others 640x480_80x24_mono --no-cpu --no-wire --no-d2h --batch-sweep '' --no-hot --extra $O/extra_$rep.json > $O/line_$rep.txt 2>> $O/stderr.txt
+timeout 300 python3 bench.py --full --others 640x480_80x24_mono --no-cpu --no-wire --no-d2h --batch-sweep '' --no-hot --extra $O/extra_$rep.json > $O/line_$rep.txt 2>> $O/stderr.txt
 python3 -c "
 import json; d=json.load(open('$O/extra_$rep.json')); 
 for w in d.get('other_workloads', d.get('others', [])):

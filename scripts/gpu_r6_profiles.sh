@@ -7,7 +7,7 @@
 TAG=${1:-r6prof}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 python3 scripts/source_id.py > $OUT/source_id.txt   # what the traces were taken on (bench.py drops a stale frac_profile)
-COMMON="--warmup 5 --no-cpu --no-d2h --no-hot --no-wire --others none --batch-sweep= --extra ''"
+COMMON="--full --warmup 5 --no-cpu --no-d2h --no-hot --no-wire --others none --batch-sweep= --extra ''"
 reduce() { # name
   local csvf=$(find $OUT/t_$1 -name "*kernel_trace.csv" | head -1)
   if [ -n "$csvf" ]; then python scripts/trace_stats.py $csvf $OUT/${1}_kernel_stats.csv $OUT/${1}_trace_overlap.json > /dev/null; else echo "$1: no trace"; fi
@@ -70,4 +70,4 @@ PY
   pmc k6_4k_write WRITE_SIZE --workload 4k_640x180_halfblock --input-sets 4 --streams 4; } | tee $OUT/pmc_summary.txt
 # the driver's own command, twice (the round's bench line as the driver will see it)
 cd $GRAFT_REPO_ROOT
-for i in 1 2; do timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --extra $OUT/bench_extra_driver_flags_$i.json > $OUT/bench_driver_stdout_$i.txt 2> $OUT/bench_driver_stderr_$i.txt; tail -c 600 $OUT/bench_driver_stdout_$i.txt; done
+for i in 1 2; do timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --extra $OUT/bench_extra_driver_flags_$i.json > $OUT/bench_driver_stdout_$i.txt 2> $OUT/bench_driver_stderr_$i.txt; tail -c 600 $OUT/bench_driver_stdout_$i.txt; done

@@ -98,7 +98,7 @@ def _bench_ranks_on_shared_gpus(n, tmp_path):
     env = dict(os.environ, ASCIICHAT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", ASCIICHAT_HIP_RCCL_LIB=build_loopback())
     extra = tmp_path / "extra.json"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "5", "--warmup", "2", "--batch", "64",
-           "--input-sets", "4", "--no-cpu", "--no-d2h", "--no-hot", "--no-wire", "--others", "none", "--extra", str(extra)]
+           "--input-sets", "4", "--full", "--no-cpu", "--no-d2h", "--no-hot", "--no-wire", "--others", "none", "--extra", str(extra)]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
