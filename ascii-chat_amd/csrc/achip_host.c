@@ -692,14 +692,14 @@ static long extent(const launch_facts_t *F, int variant) { return achip_uniform_
 /* Whether a forced geometry can render the launch, for all three families; ids that are no geometry are refused.  The
  * stream and rows geometries then render whole frames only; a phase geometry may still be cut into row bands. */
 static bool forced_applies(const launch_facts_t *F, const int *variant_caps, int id) {
-  if (id >= 0 && id < ACHIP_VARIANT_COUNT) /* (no half-block instantiations in the 512- / 256-thread geometries: render_inst.hip has_mode) */
-    return F->max_wp <= variant_caps[id] && !(F->hb && (id == 1 || id == 2));
-  if (stream_cpl(id)) /* (truecolor-fg with multi-byte glyphs: render_stream_inst.hip HAS_U8) */
+  if (id >= 0 && id < ACHIP_VARIANT_COUNT) /* (no half-block instantiations in the 512- / 256-thread geometries) */
+    return F->max_wp <= variant_caps[id] && !(F->hb && !ACHIP_FRAME_VARIANT_HALFBLOCK(id));
+  if (stream_cpl(id)) /* (truecolor-fg with multi-byte glyphs: an instantiation of its own in some geometries) */
     return F->cell_mode && F->max_cells <= (long)ACHIP_STREAM_MAXBLK * (64 * stream_cpl(id) - F->ghost) &&
-           !(F->u8_true && id != 16 && id != 17 && id != 20);
+           !(F->u8_true && !ACHIP_STREAM_VARIANT_U8(id));
   if (rows_cpl(id)) /* (geometry 26, the segment geometries and the shared-out ones carry the fast sampler only) */
     return F->run_mode && F->max_wp <= rows_max_row(id) && extent(F, id) <= ACHIP_STREAM_MAXBLK &&
-           !(F->general_sampler && (id == 26 || rows_wide_waves(id) || ACHIP_ROWS_VARIANT_PARTS(id)));
+           !(F->general_sampler && !ACHIP_ROWS_VARIANT_COMP(id));
   return false;
 }
 

@@ -1,6 +1,7 @@
 /*
- * hip_launch.hip -- plain-C launchers of the gfx950 kernels (the frame kernel itself is instantiated per
- * geometry in render_inst.hip).
+ * hip_launch.hip -- plain-C launchers of the gfx950 kernels.  The render kernels are instantiated per geometry in the
+ * render_*_inst.hip units: the render entry points check their arguments, fill a launch record (render_inst.h) and hand it
+ * to the unit of the geometry.
  * Built only with hipcc --offload-arch=gfx950; there is no host/CPU variant of these entry points.
  */
 #include "hip_launch.h"
@@ -8,12 +9,42 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
-#include <mutex>
 
+#include "launch_common.hpp"
 #include "render_inst.h"
 #include "render_stream.hpp"
 #include "crc_kernels.hpp"
 #include "render_variants.h"
+
+/* the launch to the translation unit of its geometry, over the three tables (render_variants.h) */
+static int launch_variant(int variant, const achipk_launch_t &l) {
+  switch (variant) {
+#define X(id, B, C, R)                                                                                                 \
+  case id:                                                                                                             \
+    return achipk_render_inst_launch_##id(&l);
+    ACHIP_VARIANTS(X)
+#undef X
+#define X(id, W, C)                                                                                                    \
+  case id:                                                                                                             \
+    return achipk_render_sinst_launch_##id(&l);
+    ACHIP_STREAM_VARIANTS(X)
+#undef X
+#define X(id, W, C)                                                                                                    \
+  case id:                                                                                                             \
+    return achipk_render_rinst_launch_##id(&l);
+    ACHIP_ROWS_VARIANTS(X)
+#undef X
+  }
+  return (int)hipErrorInvalidValue;
+}
+/* what every form's record starts from: one part, no wire stage, no exact-length destination */
+static achipk_launch_t launch_record(int form, int mode, int comp, const achip_frame_t *frames, int n, const achip_lut_t *lut,
+                                     uint8_t *out, uint64_t stride, uint32_t *len, const achip_uniform_t *uniform, void *stream) {
+  achipk_launch_t l = {};
+  l.form = form, l.mode = mode, l.comp = comp, l.frames = frames, l.n = n, l.lut = lut, l.out = out, l.stride = stride;
+  l.len = len, l.uniform = uniform, l.ps = {1, 1u, nullptr}, l.stream = stream;
+  return l;
+}
 
 extern "C" int achip_launch_render(int mode, int variant, int has_composite, const achip_frame_t *frames_dev, int n_frames,
                                    const achip_lut_t *lut_dev, uint8_t *out, uint64_t out_stride, uint32_t *out_len,
@@ -24,52 +55,21 @@ extern "C" int achip_launch_render(int mode, int variant, int has_composite, con
     return (int)hipSuccess;
   if (parts < 1 || (parts > 1 && (!part_sync || rows_per_part < 1)))
     return (int)hipErrorInvalidValue;
-  if (ACHIP_IS_ROWS_VARIANT(variant)) { /* wave-autonomous kernel of the run-structured modes (render_rows.hpp) */
-    /* (the profiled entry points' per-wave stamps do not exist here: prof is ignored) */
-    /* a frame's blocks shared out over `parts` workgroups: the PARTS geometry only (rows_per_part means nothing here) */
-    if (parts != 1 && (!ACHIP_ROWS_VARIANT_PARTS(variant) || parts > 64 || epoch == 0u))
-      return (int)hipErrorInvalidValue;
-    const achip_partsdev_t ps = {parts, epoch, part_sync};
-    switch (variant) {
-#define X(id, W, C)                                                                                                    \
-  case id:                                                                                                             \
-    return achipk_render_rinst_launch_##id(mode, has_composite, frames_dev, n_frames, lut_dev, out, out_stride, out_len, \
-                                          uniform, nullptr, &ps, stream);
-      ACHIP_ROWS_VARIANTS(X)
-#undef X
-    }
+  /* a frame's blocks shared out over `parts` workgroups of the stream / rows kernel: the PARTS geometries only
+   * (rows_per_part means nothing there); a frame geometry cuts the frame into row bands instead */
+  const bool blocks = ACHIP_IS_STREAM_VARIANT(variant) || ACHIP_IS_ROWS_VARIANT(variant);
+  if (blocks && parts != 1 &&
+      (!(ACHIP_IS_ROWS_VARIANT(variant) ? ACHIP_ROWS_VARIANT_PARTS(variant) : ACHIP_STREAM_VARIANT_PARTS(variant)) || parts > 64 || epoch == 0u))
     return (int)hipErrorInvalidValue;
-  }
-  if (ACHIP_IS_STREAM_VARIANT(variant)) { /* wave-autonomous kernel: per-cell modes (render_stream.hpp) */
-    if (parts != 1) { /* a frame's blocks shared out over `parts` workgroups (rows_per_part means nothing here) */
-      if (variant != 18 || parts > 64 || epoch == 0u)
-        return (int)hipErrorInvalidValue;
-      const achip_partsdev_t ps = {parts, epoch, part_sync};
-      return achipk_render_sinst_parts_launch_18(mode, has_composite, frames_dev, n_frames, lut_dev, out, out_stride, out_len, uniform,
-                                                prof, &ps, stream);
-    }
-    switch (variant) {
-#define X(id, W, C)                                                                                                    \
-  case id:                                                                                                             \
-    return achipk_render_sinst_launch_##id(mode, has_composite, frames_dev, n_frames, lut_dev, out, out_stride, out_len, \
-                                          uniform, prof, nullptr, stream);
-      ACHIP_STREAM_VARIANTS(X)
-#undef X
-    }
-    return (int)hipErrorInvalidValue;
-  }
-  switch (variant) { /* one translation unit per geometry: render_inst.hip */
-#define X(id, B, C, R)                                                                                                 \
-  case id:                                                                                                             \
-    return achipk_render_inst_launch_##id(mode, has_composite, frames_dev, n_frames, lut_dev, out, out_stride, out_len, \
-                                         prof, parts, rows_per_part, part_sync, epoch, uniform, stream);
-    ACHIP_VARIANTS(X)
-#undef X
-  }
-  return (int)hipErrorInvalidValue;
+  achipk_launch_t l = launch_record(parts > 1 ? ACHIPK_FORM_PARTS : ACHIPK_FORM_PLAIN, mode, has_composite, frames_dev, n_frames, lut_dev,
+                                    out, out_stride, out_len, uniform, stream);
+  l.prof = prof; /* (the rows kernel has no per-wave stamps: ignored there) */
+  l.ps = {parts, epoch, part_sync};
+  l.rows_per_part = rows_per_part;
+  return launch_variant(variant, l);
 }
 
-/* whole-frame launch of a per-cell mode with the frame CRC-32C riding the drain (stream geometries 16 / 17) */
+/* whole-frame launch with the frame CRC-32C riding the drain (achip_variant_has_crc) */
 extern "C" int achip_launch_render_crc(int mode, int variant, int has_composite, const achip_frame_t *frames_dev,
                                        int n_frames, const achip_lut_t *lut_dev, uint8_t *out, uint64_t out_stride,
                                        uint32_t *out_len, const achip_wire_t *wire, const achip_uniform_t *uniform,
@@ -78,22 +78,13 @@ extern "C" int achip_launch_render_crc(int mode, int variant, int has_composite,
     return (int)hipSuccess;
   if (!wire || !wire->crc)
     return (int)hipErrorInvalidValue;
-  switch (variant) {
-#define X(id, W, C)                                                                                                    \
-  case id:                                                                                                             \
-    return achipk_render_sinst_launch_##id(mode, has_composite, frames_dev, n_frames, lut_dev, out, out_stride, out_len, \
-                                          uniform, prof, wire, stream);
-    ACHIP_STREAM_VARIANTS(X)
-#undef X
-#define X(id, W, C)                                                                                                    \
-  case id:                                                                                                             \
-    return achipk_render_rinst_launch_##id(mode, has_composite, frames_dev, n_frames, lut_dev, out, out_stride, out_len,  \
-                                          uniform, wire, nullptr, stream);
-    ACHIP_ROWS_VARIANTS(X)
-#undef X
-  }
-  return (int)hipErrorInvalidValue;
+  achipk_launch_t l = launch_record(ACHIPK_FORM_CRC, mode, has_composite, frames_dev, n_frames, lut_dev, out, out_stride, out_len, uniform, stream);
+  l.prof = prof;
+  l.wire = wire;
+  return launch_variant(variant, l);
 }
+/* the exact-length forms: 1024 threads while every frame has a CU to itself (one block per wave), 512-thread workgroups
+ * otherwise (ACHIP_STREAM_EXACT_VARIANT) */
 extern "C" int achip_launch_render_pack(int mode, int variant, const achip_frame_t *frames_dev, int n_frames,
                                         const achip_lut_t *lut_dev, uint64_t bound, uint32_t *out_len, const achip_wire_t *wire,
                                         const achip_uniform_t *uniform, const achip_packdev_t *pack, void *stream) {
@@ -101,27 +92,24 @@ extern "C" int achip_launch_render_pack(int mode, int variant, const achip_frame
     return (int)hipSuccess;
   if (bound > (uint64_t)ACHIP_PACK_FRAME_CAP)
     return (int)hipErrorInvalidValue;
-  /* 1024 threads while every frame has a CU to itself (variant 16: one block per wave), 512-thread workgroups otherwise */
-  return variant == 16 ? achipk_render_sinst_pack_launch_16(mode, frames_dev, n_frames, lut_dev, bound, out_len, uniform, wire, pack, stream)
-                       : achipk_render_sinst_pack_launch_17(mode, frames_dev, n_frames, lut_dev, bound, out_len, uniform, wire, pack, stream);
+  achipk_launch_t l = launch_record(ACHIPK_FORM_PACK, mode, 0, frames_dev, n_frames, lut_dev, nullptr, bound, out_len, uniform, stream);
+  l.wire = wire;
+  l.pack = pack;
+  return launch_variant(ACHIP_STREAM_EXACT_VARIANT(variant), l);
 }
 extern "C" int achip_pack_frame_cap(void) { return ACHIP_PACK_FRAME_CAP; }
-/* exact-length truecolor frames of any size in ONE launch (render_stream.hpp LF): stream geometries 16 / 17 */
-extern "C" int achipk_render_sinst_lenfirst_launch_16(const achip_frame_t *, int, const achip_lut_t *, uint64_t, uint32_t *, const achip_uniform_t *, const achip_packdev_t *, void *);
-extern "C" int achipk_render_sinst_lenfirst_launch_17(const achip_frame_t *, int, const achip_lut_t *, uint64_t, uint32_t *, const achip_uniform_t *, const achip_packdev_t *, void *);
 extern "C" int achip_launch_render_length_first(int variant, const achip_frame_t *frames_dev, int n_frames, const achip_lut_t *lut_dev,
                                                 uint64_t bound, uint32_t *out_len, const achip_uniform_t *uniform,
                                                 const achip_packdev_t *pack, void *stream) {
   if (n_frames <= 0)
     return (int)hipSuccess;
-  return variant == 16 ? achipk_render_sinst_lenfirst_launch_16(frames_dev, n_frames, lut_dev, bound, out_len, uniform, pack, stream)
-                       : achipk_render_sinst_lenfirst_launch_17(frames_dev, n_frames, lut_dev, bound, out_len, uniform, pack, stream);
+  achipk_launch_t l = launch_record(ACHIPK_FORM_LENFIRST, ACHIP_MODE_TRUE_FG, 0, frames_dev, n_frames, lut_dev, nullptr, bound, out_len, uniform, stream);
+  l.pack = pack;
+  return launch_variant(ACHIP_STREAM_EXACT_VARIANT(variant), l);
 }
-#ifdef ACHIP_ALL_GEOMETRIES
-extern "C" int achip_variant_has_crc(int variant) { return variant == 16 || variant == 17 || (ACHIP_IS_ROWS_VARIANT(variant) && variant != 26 && !ACHIP_ROWS_VARIANT_WIDE(variant) && !ACHIP_ROWS_VARIANT_PARTS(variant)); }
-#else
-extern "C" int achip_variant_has_crc(int variant) { return variant == 16 || variant == 17; }
-#endif
+extern "C" int achip_variant_has_crc(int variant) {
+  return ACHIP_STREAM_VARIANT_CRC(variant) || (ACHIP_IS_ROWS_VARIANT(variant) && ACHIP_ROWS_VARIANT_CRC(variant));
+}
 /* ... and whether riding the drain beats a second pass over the slab there (measured, profiles/r03_rows_kernel.txt): yes
  * for the per-cell modes' stream kernel (+2.4 us against +8.3 us per 256-frame step); no for the rows kernel, whose
  * per-slice checksum chains cost more than the stand-alone kernel's pass (+12 against +8 us on 80x24 half blocks, +240
@@ -380,35 +368,12 @@ extern "C" int achip_crc_parts(uint32_t max_len, int n) {
 }
 
 /* the prebuilt tables of the checksum kernels (crc_math.hpp: crc_frame_tables_init_kernel<BLOCK>: slicing tables, the Horner
- * table of a BLOCK-thread workgroup, the power tables), one image per device and BLOCK */
+ * table of a BLOCK-thread workgroup, the power tables), one image per device and BLOCK for the whole library (launch_common.hpp) */
 template <int BLOCK> static hipError_t frame_crc_tables(const uint4 **out) {
-  constexpr int MAX_DEVICES = 16;
-  static std::mutex mu;
-  static uint32_t *tab[MAX_DEVICES] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess)
-    return e;
-  if (dev < 0 || dev >= MAX_DEVICES)
-    return hipErrorInvalidDevice;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!tab[dev]) {
-    uint32_t *t = nullptr;
-    e = hipMalloc(reinterpret_cast<void **>(&t), (size_t)ACHIP_FRAME_CRC_TAB_BYTES);
-    if (e != hipSuccess)
-      return e;
-    hipLaunchKernelGGL((achip::crc_frame_tables_init_kernel<BLOCK>), dim3(1), dim3(256), ACHIP_FRAME_CRC_TAB_BYTES, nullptr, t);
-    e = hipGetLastError();
-    if (e == hipSuccess)
-      e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-      (void)hipFree(t);
-      return e;
-    }
-    tab[dev] = t;
-  }
-  *out = reinterpret_cast<const uint4 *>(tab[dev]);
-  return hipSuccess;
+  return achip::device_table<achip::crc_frame_tables_init_kernel<BLOCK>, ACHIP_FRAME_CRC_TAB_BYTES, ACHIP_FRAME_CRC_TAB_BYTES>(out);
+}
+extern "C" int achipk_frame_crc_tables(int block, const uint4 **out) {
+  return (int)(block == 1024 ? frame_crc_tables<1024>(out) : block == 256 ? frame_crc_tables<256>(out) : hipErrorInvalidValue);
 }
 
 /* Builds this device's table images NOW (plan_create calls it): the first checksum / wire / pack call of a process would

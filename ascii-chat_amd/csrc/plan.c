@@ -739,7 +739,7 @@ static int plan_render_pack(asciichat_hip_plan_t *p, uint32_t *out_len_dev, cons
  * sources up to 1080p, device destinations, callers that receive off_out (completion order, like the PACK form). */
 static int plan_length_first_ok(const asciichat_hip_plan_t *p) {
   return p->mode == ACHIP_MODE_TRUE_FG && p->palette_ascii && !p->has_comp && plan_frames_whole(p) &&
-         (p->whole_variant == 16 || p->whole_variant == 17);
+         ACHIP_STREAM_VARIANT_EXACT(p->whole_variant);
 }
 /* whether plan_render_packed / _packets_packed may take the length-first form for this plan (frames beyond the one-launch
  * form's 48 KB; the automatic setting adds: dense sources, a device destination) */

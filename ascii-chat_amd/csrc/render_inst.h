@@ -1,5 +1,6 @@
-/* render_inst.h -- entry points of the per-geometry translation units (render_inst.hip, -DACHIP_INST=id).  Their names
- * start with achipk_, not achip_: they are the library's own plumbing and stay local (exports.map). */
+/* render_inst.h -- the launch record and the entry points of the per-geometry translation units (render_inst.hip,
+ * render_stream_inst.hip, render_rows_inst.hip): one `launch` and one `lds` function each.  Their names start with achipk_, not
+ * achip_: they are the library's own plumbing and stay local (exports.map). */
 #ifndef ACHIP_RENDER_INST_H
 #define ACHIP_RENDER_INST_H
 
@@ -12,96 +13,95 @@
 extern "C" {
 #endif
 
-/* four translation units per geometry: _p0 = modes 0..2 (mono, truecolor / 256-colour foreground), _p1 = 3, 4 (16-colour
- * foreground, truecolor background), _p2 = 5..7 (the coloured half-block modes), _p3 = 8, 9 (mono half blocks, dither) */
+/* What a render launch can carry: the entry points of hip_launch.h fill one, every translation unit takes it whole and
+ * answers hipErrorInvalidValue for a form it does not instantiate */
+enum {
+  ACHIPK_FORM_PLAIN = 0, /* whole frames into a slab                                                                     */
+  ACHIPK_FORM_PARTS,     /* a frame shared out over ps.parts > 1 workgroups: row bands of rows_per_part text rows (frame
+                            geometries), runs of blocks (stream / rows PARTS geometries, which read `ps` as one part too) */
+  ACHIPK_FORM_CRC,       /* whole frames, the frame CRC riding the drain: `wire` (wire->crc required)                    */
+  ACHIPK_FORM_PACK,      /* stream kernel: exact-length frames staged in LDS, into `pack`; `wire` optional; no slab       */
+  ACHIPK_FORM_LENFIRST   /* stream kernel: exact-length truecolor frames of any size, into `pack`; no slab                */
+};
+typedef struct {
+  int form, mode, comp; /* comp: some frame samples a virtual composite (the general sampler) */
+  const achip_frame_t *frames;
+  int n;
+  const achip_lut_t *lut;
+  uint8_t *out;    /* the slab; NULL for the exact-length forms                                  */
+  uint64_t stride; /* of the slab; for the exact-length forms the bound of a frame's length       */
+  uint32_t *len;
+  const achip_uniform_t *uniform; /* NULL, or the batch's common descriptor / launch-wide flags */
+  unsigned long long *prof;       /* NULL, or 8 u64 per frame (diagnostics; the rows kernel has none) */
+  const achip_wire_t *wire;
+  const achip_packdev_t *pack;
+  achip_partsdev_t ps; /* {1, 1, NULL} unless shared out */
+  int rows_per_part;
+  void *stream;
+} achipk_launch_t;
+
+/* four translation units per frame geometry (render_inst.hip, -DACHIP_INST=id -DACHIP_PART=p): _p0 = modes 0..2 (mono,
+ * truecolor / 256-colour foreground), _p1 = 3, 4 (16-colour foreground, truecolor background), _p2 = 5..7 (the coloured
+ * half-block modes), _p3 = 8, 9 (mono half blocks, dither) */
 #define ACHIP_INST_PART_OF(m) ((m) <= 2 ? 0 : (m) <= 4 ? 1 : (m) <= 7 ? 2 : 3)
-#define ACHIP_INST_ARGS                                                                                                \
-  int mode, int comp, const achip_frame_t *frames, int n, const achip_lut_t *lut, uint8_t *out, uint64_t stride,       \
-      uint32_t *len, unsigned long long *prof, int parts, int rows_per_part, unsigned long long *part_sync,            \
-      uint32_t epoch, const achip_uniform_t *uniform, void *stream
-#define ACHIP_INST_PASS mode, comp, frames, n, lut, out, stride, len, prof, parts, rows_per_part, part_sync, epoch, uniform, stream
-#define X(id, B, C, R)                                                                                                 \
-  int achipk_render_inst_launch_##id##_p0(ACHIP_INST_ARGS);                                                             \
-  int achipk_render_inst_launch_##id##_p1(ACHIP_INST_ARGS);                                                             \
-  int achipk_render_inst_launch_##id##_p2(ACHIP_INST_ARGS);                                                             \
-  int achipk_render_inst_launch_##id##_p3(ACHIP_INST_ARGS);                                                             \
-  int achipk_render_inst_lds_##id##_p0(int mode);                                                                       \
-  int achipk_render_inst_lds_##id##_p1(int mode);                                                                       \
-  int achipk_render_inst_lds_##id##_p2(int mode);                                                                       \
-  int achipk_render_inst_lds_##id##_p3(int mode);                                                                       \
-  static inline int achipk_render_inst_launch_##id(ACHIP_INST_ARGS) {                                                   \
-    switch (ACHIP_INST_PART_OF(mode)) {                                                                                \
-    case 0: return achipk_render_inst_launch_##id##_p0(ACHIP_INST_PASS);                                                \
-    case 1: return achipk_render_inst_launch_##id##_p1(ACHIP_INST_PASS);                                                \
-    case 2: return achipk_render_inst_launch_##id##_p2(ACHIP_INST_PASS);                                                \
-    default: return achipk_render_inst_launch_##id##_p3(ACHIP_INST_PASS);                                               \
-    }                                                                                                                  \
-  }                                                                                                                    \
-  static inline int achipk_render_inst_lds_##id(int mode) {                                                             \
-    switch (ACHIP_INST_PART_OF(mode)) {                                                                                \
-    case 0: return achipk_render_inst_lds_##id##_p0(mode);                                                              \
-    case 1: return achipk_render_inst_lds_##id##_p1(mode);                                                              \
-    case 2: return achipk_render_inst_lds_##id##_p2(mode);                                                              \
-    default: return achipk_render_inst_lds_##id##_p3(mode);                                                             \
-    }                                                                                                                  \
-  }
+#define ACHIP_INST_PARTS(Y, id) Y(id, 0) Y(id, 1) Y(id, 2) Y(id, 3)
+#define Y(id, p)                                                                                                       \
+  int achipk_render_inst_launch_##id##_p##p(const achipk_launch_t *l);                                                  \
+  int achipk_render_inst_lds_##id##_p##p(int mode);
+#define X(id, B, C, R) ACHIP_INST_PARTS(Y, id)
 ACHIP_VARIANTS(X)
 #undef X
+#undef Y
 
-/* the stream-kernel geometries (render_stream_inst.hip, -DACHIP_SINST=id) */
+/* the stream-kernel geometries (render_stream_inst.hip, -DACHIP_SINST=id): one unit per geometry, every form it carries */
 #define X(id, W, C)                                                                                                    \
-  int achipk_render_sinst_launch_##id(int mode, int comp, const achip_frame_t *frames, int n, const achip_lut_t *lut,   \
-                                     uint8_t *out, uint64_t stride, uint32_t *len, const achip_uniform_t *uniform,     \
-                                     unsigned long long *prof, const achip_wire_t *wire, void *stream);                                                                    \
+  int achipk_render_sinst_launch_##id(const achipk_launch_t *l);                                                        \
   int achipk_render_sinst_lds_##id(int mode);
 ACHIP_STREAM_VARIANTS(X)
 #undef X
 
-/* the PACK instantiations of stream geometries 16 and 17 (render_stream_inst.hip with -DACHIP_SINST=16 / 17) */
-int achipk_render_sinst_pack_launch_16(int mode, const achip_frame_t *frames, int n, const achip_lut_t *lut, uint64_t stride,
-                                      uint32_t *len, const achip_uniform_t *uniform, const achip_wire_t *wire,
-                                      const achip_packdev_t *pack, void *stream);
-int achipk_render_sinst_pack_launch_17(int mode, const achip_frame_t *frames, int n, const achip_lut_t *lut, uint64_t stride,
-                                      uint32_t *len, const achip_uniform_t *uniform, const achip_wire_t *wire,
-                                      const achip_packdev_t *pack, void *stream);
-
-/* the PARTS instantiations of stream geometry 18 (a frame's blocks shared out over ps->parts workgroups, 2..64) */
-int achipk_render_sinst_parts_launch_18(int mode, int comp, const achip_frame_t *frames, int n, const achip_lut_t *lut,
-                                       uint8_t *out, uint64_t stride, uint32_t *len, const achip_uniform_t *uniform,
-                                       unsigned long long *prof, const achip_partsdev_t *ps, void *stream);
-
 /* the rows-kernel geometries (render_rows_inst.hip, -DACHIP_RINST=id -DACHIP_RMODE=mode): run-structured modes, whole
  * frames; one translation unit per (geometry, mode) */
-#define ACHIP_RINST_ARGS                                                                                               \
-  int mode, int comp, const achip_frame_t *frames, int n, const achip_lut_t *lut, uint8_t *out, uint64_t stride,       \
-      uint32_t *len, const achip_uniform_t *uniform, const achip_wire_t *wire, const achip_partsdev_t *ps, void *stream
 #define ACHIP_RINST_MODES(Y, id) Y(id, 0) Y(id, 5) Y(id, 6) Y(id, 7) Y(id, 8) /* mono, the four half-block modes */
 #define Y(id, m)                                                                                                       \
-  int achipk_render_rinst_launch_##id##_m##m(ACHIP_RINST_ARGS);                                                         \
+  int achipk_render_rinst_launch_##id##_m##m(const achipk_launch_t *l);                                                 \
   int achipk_render_rinst_lds_##id##_m##m(int mode);
 #define X(id, W, C) ACHIP_RINST_MODES(Y, id)
 ACHIP_ROWS_VARIANTS(X)
 #undef X
 #undef Y
-#define Y(id, m)                                                                                                       \
-  case m:                                                                                                              \
-    return achipk_render_rinst_launch_##id##_m##m(mode, comp, frames, n, lut, out, stride, len, uniform, wire, ps, stream);
-#define Z(id, m)                                                                                                       \
-  case m:                                                                                                              \
-    return achipk_render_rinst_lds_##id##_m##m(mode);
+
+/* a geometry's units as one: the unit of the launch's mode */
+#define YL(id, p) case p: return achipk_render_inst_launch_##id##_p##p(l);
+#define ZL(id, p) case p: return achipk_render_inst_lds_##id##_p##p(mode);
+#define X(id, B, C, R)                                                                                                 \
+  static inline int achipk_render_inst_launch_##id(const achipk_launch_t *l) {                                          \
+    switch (ACHIP_INST_PART_OF(l->mode)) { ACHIP_INST_PARTS(YL, id) }                                                  \
+    return 1; /* hipErrorInvalidValue */                                                                               \
+  }                                                                                                                    \
+  static inline int achipk_render_inst_lds_##id(int mode) {                                                             \
+    switch (ACHIP_INST_PART_OF(mode)) { ACHIP_INST_PARTS(ZL, id) }                                                     \
+    return -1;                                                                                                         \
+  }
+ACHIP_VARIANTS(X)
+#undef X
+#undef YL
+#undef ZL
+#define YL(id, m) case m: return achipk_render_rinst_launch_##id##_m##m(l);
+#define ZL(id, m) case m: return achipk_render_rinst_lds_##id##_m##m(mode);
 #define X(id, W, C)                                                                                                    \
-  static inline int achipk_render_rinst_launch_##id(ACHIP_RINST_ARGS) {                                                 \
-    switch (mode) { ACHIP_RINST_MODES(Y, id) }                                                                         \
+  static inline int achipk_render_rinst_launch_##id(const achipk_launch_t *l) {                                         \
+    switch (l->mode) { ACHIP_RINST_MODES(YL, id) }                                                                     \
     return 1; /* hipErrorInvalidValue */                                                                               \
   }                                                                                                                    \
   static inline int achipk_render_rinst_lds_##id(int mode) {                                                            \
-    switch (mode) { ACHIP_RINST_MODES(Z, id) }                                                                         \
+    switch (mode) { ACHIP_RINST_MODES(ZL, id) }                                                                        \
     return -1;                                                                                                         \
   }
 ACHIP_ROWS_VARIANTS(X)
 #undef X
-#undef Y
-#undef Z
+#undef YL
+#undef ZL
 
 #ifdef __cplusplus
 }

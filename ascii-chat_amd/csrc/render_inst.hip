@@ -1,10 +1,12 @@
 /*
  * render_inst.hip -- instantiates the frame kernel for ONE geometry (-DACHIP_INST=<variant id>): ten modes x
- * {plain, composite sampler} x {whole-frame, row-band} launches.  One translation unit per geometry so that
- * the build runs in parallel (make -j).  Built only with hipcc --offload-arch=gfx950.
+ * {plain, composite sampler} x {whole-frame, row-band} launches, behind one launcher that takes the launch record
+ * (render_inst.h).  One translation unit per geometry so that the build runs in parallel (make -j).  Built only with
+ * hipcc --offload-arch=gfx950.
  */
 #include <hip/hip_runtime.h>
 
+#include "launch_common.hpp"
 #include "render_inst.h"
 #define ACHIP_FRAME_KERNEL_ONLY
 #include "render_kernels.hpp"
@@ -26,54 +28,33 @@ ACHIP_VARIANTS(X)
 #undef X
 using G = Geometry<ACHIP_INST>;
 
-/* row bands are only ever launched with the geometries the host policy picks for them (achip_choose_geometry) */
-constexpr bool HAS_SPLIT = ACHIP_INST == 1 || ACHIP_INST == 2 || ACHIP_INST == 4;
-/* the half-block modes never run in the 512- / 256-thread geometries (they need more than the 128 VGPRs that make those
- * geometries worthwhile; the host policy sends them to the 1024-thread one, the wide one or the rows kernel): those
- * instantiations do not exist */
+/* row bands / the half-block modes: instantiated only where a launch can take them (render_variants.h) */
+constexpr bool HAS_SPLIT = ACHIP_FRAME_VARIANT_BANDS(ACHIP_INST);
 template <int MODE> constexpr bool has_mode() {
-  return ACHIP_IN_PART(MODE) && !(achip::mode_is_halfblock(MODE) && (ACHIP_INST == 1 || ACHIP_INST == 2));
+  return ACHIP_IN_PART(MODE) && (!achip::mode_is_halfblock(MODE) || ACHIP_FRAME_VARIANT_HALFBLOCK(ACHIP_INST));
 }
 
-template <int MODE, bool COMP, bool SPLIT>
-hipError_t launch_one(const achip_frame_t *frames, int n, const achip_lut_t *lut, uint8_t *out, uint64_t stride,
-                      uint32_t *len, unsigned long long *prof, int parts, int rows_per_part, unsigned long long *part_sync,
-                      uint32_t epoch, const achip_uniform_t &uni, hipStream_t stream) {
+template <int MODE, bool COMP, bool SPLIT> hipError_t launch_one(const achipk_launch_t &l, const achip_uniform_t &uni) {
   using L = achip::Lds<MODE, G::BLOCK, G::CAP, G::RING>;
-  auto kern = achip::render_frames_kernel<MODE, G::BLOCK, G::CAP, G::RING, COMP, SPLIT>;
-  static bool attr_set = false; /* one flag per instantiation; benign race (idempotent call) */
-  if (!attr_set) {
-    if (L::bytes > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, L::bytes);
-      if (e != hipSuccess)
-        return e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)n * (unsigned)parts), dim3(G::BLOCK), (size_t)L::bytes, stream, frames, lut,
-                     out, stride, len, n, prof, parts, rows_per_part, part_sync, epoch, uni);
+  constexpr auto kern = achip::render_frames_kernel<MODE, G::BLOCK, G::CAP, G::RING, COMP, SPLIT>;
+  const hipError_t e = achip::ensure_dynamic_lds<kern>(L::bytes);
+  if (e != hipSuccess)
+    return e;
+  const int parts = SPLIT ? l.ps.parts : 1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)l.n * (unsigned)parts), dim3(G::BLOCK), (size_t)L::bytes, static_cast<hipStream_t>(l.stream),
+                     l.frames, l.lut, l.out, l.stride, l.len, l.n, l.prof, parts, l.rows_per_part, SPLIT ? l.ps.sync : nullptr,
+                     l.ps.epoch, uni);
   return hipGetLastError();
 }
 
-template <int MODE>
-hipError_t launch_mode(bool comp, const achip_frame_t *frames, int n, const achip_lut_t *lut, uint8_t *out,
-                       uint64_t stride, uint32_t *len, unsigned long long *prof, int parts, int rows_per_part,
-                       unsigned long long *part_sync, uint32_t epoch, const achip_uniform_t &uni, hipStream_t stream) {
-  if (parts > 1) {
-    if constexpr (HAS_SPLIT) {
-      return comp ? launch_one<MODE, true, true>(frames, n, lut, out, stride, len, prof, parts, rows_per_part, part_sync,
-                                                 epoch, uni, stream)
-                  : launch_one<MODE, false, true>(frames, n, lut, out, stride, len, prof, parts, rows_per_part,
-                                                  part_sync, epoch, uni, stream);
-    } else {
+template <int MODE> hipError_t launch_mode(const achipk_launch_t &l, const achip_uniform_t &uni) {
+  if (l.form == ACHIPK_FORM_PARTS) {
+    if constexpr (HAS_SPLIT)
+      return l.comp ? launch_one<MODE, true, true>(l, uni) : launch_one<MODE, false, true>(l, uni);
+    else
       return hipErrorInvalidValue;
-    }
   }
-  return comp ? launch_one<MODE, true, false>(frames, n, lut, out, stride, len, prof, 1, rows_per_part, nullptr, epoch,
-                                              uni, stream)
-              : launch_one<MODE, false, false>(frames, n, lut, out, stride, len, prof, 1, rows_per_part, nullptr, epoch,
-                                               uni, stream);
+  return l.comp ? launch_one<MODE, true, false>(l, uni) : launch_one<MODE, false, false>(l, uni);
 }
 
 } // namespace
@@ -81,22 +62,15 @@ hipError_t launch_mode(bool comp, const achip_frame_t *frames, int n, const achi
 #define ACHIP_CAT2(a, b) a##b
 #define ACHIP_CAT(a, b) ACHIP_CAT2(a, b)
 
-extern "C" int ACHIP_CAT(ACHIP_CAT(ACHIP_CAT(achipk_render_inst_launch_, ACHIP_INST), _p), ACHIP_PART)(int mode, int comp, const achip_frame_t *frames, int n,
-                                                                const achip_lut_t *lut, uint8_t *out, uint64_t stride,
-                                                                uint32_t *len, unsigned long long *prof, int parts,
-                                                                int rows_per_part, unsigned long long *part_sync,
-                                                                uint32_t epoch, const achip_uniform_t *uniform,
-                                                                void *stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  achip_uniform_t uni = {};
-  if (uniform && uniform->enabled) /* (composite batches too: achip_frames_uniform) */
-    uni = *uniform;
-  switch (mode) {
+extern "C" int ACHIP_CAT(ACHIP_CAT(ACHIP_CAT(achipk_render_inst_launch_, ACHIP_INST), _p), ACHIP_PART)(const achipk_launch_t *l) {
+  if (l->form != ACHIPK_FORM_PLAIN && l->form != ACHIPK_FORM_PARTS) /* (no checksum, no exact-length form in the phase kernel) */
+    return (int)hipErrorInvalidValue;
+  const achip_uniform_t uni = achip::launch_uniform(l->uniform);
+  switch (l->mode) {
 #define M(m)                                                                                                           \
   case m:                                                                                                              \
     if constexpr (has_mode<m>())                                                                                       \
-      return (int)launch_mode<m>(comp != 0, frames, n, lut, out, stride, len, prof, parts, rows_per_part, part_sync,   \
-                                 epoch, uni, s);                                                                       \
+      return (int)launch_mode<m>(*l, uni);                                                                             \
     else                                                                                                               \
       return (int)hipErrorInvalidValue;
     M(ACHIP_MODE_MONO)

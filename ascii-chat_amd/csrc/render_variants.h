@@ -110,4 +110,30 @@
 /* the geometries that share a frame's blocks out over several workgroups (render_rows.hpp PARTS; 33: the emulator's) */
 #define ACHIP_ROWS_VARIANT_PARTS(v) ((v) == 31 || (v) == 32 || (v) == 33 || (v) == 34)
 
+/* What a geometry's translation unit instantiates besides the plain whole-frame launch (constant expressions; the launchers,
+ * the plan, the host's policy and the test runtimes all ask here):
+ * frame geometries -- row bands only where the host policy picks them (achip_choose_geometry); the half-block modes never in
+ * the 512- / 256-thread geometries (they need more than the 128 VGPRs that make those worthwhile) */
+#define ACHIP_FRAME_VARIANT_BANDS(v) ((v) == 1 || (v) == 2 || (v) == 4)
+#define ACHIP_FRAME_VARIANT_HALFBLOCK(v) ((v) != 1 && (v) != 2)
+/* stream geometries -- the frame CRC riding the drain and the exact-length forms (PACK, length-first) in the two the policy
+ * picks by itself (an exact-length launch of any other geometry takes 17's: ACHIP_STREAM_EXACT_VARIANT); the multi-byte-palette
+ * form of truecolor foreground there and in the emulator's; a frame's blocks shared out over workgroups (PARTS) in the
+ * four-wave one -- a wave per SIMD */
+#define ACHIP_STREAM_VARIANT_CRC(v) ((v) == 16 || (v) == 17)
+#define ACHIP_STREAM_VARIANT_EXACT(v) ((v) == 16 || (v) == 17)
+#define ACHIP_STREAM_EXACT_VARIANT(v) ((v) == 16 ? 16 : 17) /* 1024 threads while a wave has one block, else 512 */
+#define ACHIP_STREAM_VARIANT_U8(v) ((v) == 16 || (v) == 17 || (v) == 20)
+#define ACHIP_STREAM_VARIANT_PARTS(v) ((v) == 18)
+/* rows geometries -- the composite (general) sampler everywhere but in the sixteen-wave geometry, the segment geometries and
+ * the shared-out ones (achip_choose_geometry never takes those for composites / 1x1 sources); the frame CRC riding the drain
+ * in the same ones, but it costs more than the stand-alone pass (achip_variant_crc_pays), no plan takes it by itself, and so it
+ * is built with -DACHIP_ALL_GEOMETRIES only */
+#define ACHIP_ROWS_VARIANT_COMP(v) ((v) != 26 && !ACHIP_ROWS_VARIANT_WIDE(v) && !ACHIP_ROWS_VARIANT_PARTS(v))
+#ifdef ACHIP_ALL_GEOMETRIES
+#define ACHIP_ROWS_VARIANT_CRC(v) ACHIP_ROWS_VARIANT_COMP(v)
+#else
+#define ACHIP_ROWS_VARIANT_CRC(v) 0
+#endif
+
 #endif

@@ -20,7 +20,7 @@ extern "C" int achip_launch_render(int mode, int variant, int has_composite, con
   (void)phase_cycles, (void)stream;
   if (n_frames <= 0)
     return MOCK_OK;
-  if ((variant == 26 || ACHIP_ROWS_VARIANT_WIDE(variant) || ACHIP_ROWS_VARIANT_PARTS(variant)) && has_composite) /* as the product's launcher: the sixteen-wave rows geometry and the segment geometries carry the fast sampler only (render_rows_inst.hip) */
+  if (ACHIP_IS_ROWS_VARIANT(variant) && !ACHIP_ROWS_VARIANT_COMP(variant) && has_composite) /* as the product's launcher: the sixteen-wave rows geometry and the segment geometries carry the fast sampler only (render_variants.h) */
     return MOCK_INVALID;
   std::lock_guard<std::mutex> lock(g_emu_mu);
   const int was = emu_set_uniform(uniform && uniform->enabled ? 1 : 0);
@@ -105,7 +105,7 @@ extern "C" int achip_launch_packets_from_crc(const uint32_t *len, const uint32_t
                  [&] { achip::crc_packets_kernel(len, crc, dims, n, hdr_out, pkt_out); });
   return MOCK_OK;
 }
-extern "C" int achip_variant_has_crc(int variant) { return variant == 16 || variant == 17 || (ACHIP_IS_ROWS_VARIANT(variant) && !ACHIP_ROWS_VARIANT_WIDE(variant) && !ACHIP_ROWS_VARIANT_PARTS(variant)); }
+extern "C" int achip_variant_has_crc(int variant) { return ACHIP_STREAM_VARIANT_CRC(variant) || (ACHIP_IS_ROWS_VARIANT(variant) && ACHIP_ROWS_VARIANT_CRC(variant)); } /* (as the all-geometries product) */
 extern "C" int achip_variant_crc_pays(int variant) { return variant == 16 || variant == 17; }
 extern "C" int achip_launch_render_crc(int mode, int variant, int has_composite, const achip_frame_t *frames, int n,
                                        const achip_lut_t *lut, uint8_t *out, uint64_t stride, uint32_t *out_len,
@@ -136,7 +136,7 @@ extern "C" int achip_launch_render_pack(int mode, int variant, const achip_frame
   if (!pack || !pack->dst || !pack->cursor || bound > 48 * 1024 || (wire && !wire->crc))
     return MOCK_INVALID;
   std::lock_guard<std::mutex> lock(g_emu_mu);
-  const int rc = emu_render_stream_pack(mode, variant == 16 ? 16 : 17, frames, n, lut, bound, out_len, wire ? wire->crc : nullptr,
+  const int rc = emu_render_stream_pack(mode, ACHIP_STREAM_EXACT_VARIANT(variant), frames, n, lut, bound, out_len, wire ? wire->crc : nullptr,
                                         wire ? wire->dims : nullptr, wire ? wire->hdr : nullptr, wire ? wire->pkt_crc : nullptr,
                                         pack->dst, pack->capacity, pack->off_out, pack->len_out, pack->cursor);
   return rc == 0 ? MOCK_OK : MOCK_INVALID;
@@ -154,7 +154,7 @@ extern "C" int achip_launch_render_length_first(int variant, const achip_frame_t
   if (!pack || !pack->dst || !pack->cursor)
     return MOCK_INVALID;
   std::lock_guard<std::mutex> lock(g_emu_mu);
-  const int rc = emu_render_stream_lenfirst(variant == 16 ? 16 : 17, frames, n, lut, bound, out_len, pack->dst, pack->capacity, pack->off_out,
+  const int rc = emu_render_stream_lenfirst(ACHIP_STREAM_EXACT_VARIANT(variant), frames, n, lut, bound, out_len, pack->dst, pack->capacity, pack->off_out,
                                             pack->len_out, pack->cursor);
   return rc == 0 ? MOCK_OK : MOCK_INVALID;
 }
