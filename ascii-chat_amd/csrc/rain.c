@@ -323,7 +323,7 @@ int asciichat_hip_rain_apply_batch(digital_rain_t *const *rains, const float *dt
                    ((uint32_t)(r->first_frame ? 1 : 0) << 24);
       d[i].num_columns = r->num_columns;
       d[i].num_rows = r->num_rows;
-      d[i].pad = 0;
+      d[i].backup = (uint32_t)((size_t)c->cols * (size_t)c->rows);
       r->first_frame = false;
       const long entries = (long)r->num_columns * (long)(r->num_rows + 1);
       if (entries <= ACHIP_RAIN_TABLE_MAX && entries > table)

@@ -11,13 +11,14 @@ extern "C" {
 
 /* one frame of a rain batch: the context's device state and its parameters as they stood at issue time */
 typedef struct {
-  float *state;       /* num_columns * num_rows previous brightness values (row-major), then as many of backup */
+  float *state;       /* num_columns * num_rows previous brightness values (row-major), and the backup half at [backup] */
   const float *cols;  /* num_columns x {time_offset, speed_multiplier} */
   float t;            /* time after this call's advance */
   float fall_speed, raindrop_length, decay;
   uint32_t color;     /* r | g << 8 | b << 16 | first_frame << 24 */
   int32_t num_columns, num_rows;
-  int32_t pad;
+  uint32_t backup;    /* cells of the grid as allocated: a grid written smaller keeps its backup behind all of them;
+                         0, or anything less than the grid as written: directly behind the grid as written */
 } achip_rain_desc_t;
 
 #define ACHIP_RAIN_BLOCK 256       /* threads per workgroup: one workgroup per frame */

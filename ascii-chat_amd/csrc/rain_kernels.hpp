@@ -21,7 +21,9 @@
  * (a barrier between them), and a cell's events never span two frames of one launch (one context per launch and frame).
  *
  * A frame whose output may not fit its slot (20 * len + 1 > dst_stride) first copies its state to the backup half of the
- * state block and copies it back when it did not fit: such a frame leaves the state as it found it.
+ * state block and copies it back when it did not fit: such a frame leaves the state as it found it.  The backup half starts
+ * behind the grid as ALLOCATED (desc.backup cells): a grid written smaller than that leaves the cells beyond it alone, as
+ * the reference does.  A descriptor that leaves the field 0 has its backup directly behind the grid as written.
  *
  * Floating point follows the reference's source order in binary32 without contraction; division is correctly rounded
  * (hipcc's default for HIP).  Only plain HIP: the same source runs under the CPU emulator (tests/hipemu).
@@ -344,9 +346,11 @@ __global__ void __launch_bounds__(256)
   const uint32_t color = d.color & 0xFFFFFFu;
   const size_t cells = (size_t)R.ncol * (size_t)R.nrow;
   const bool may_overflow = 20ull * len + 1ull > dst_stride;
+  /* never inside the live cells: a descriptor that leaves the field 0 gets the backup directly behind the grid as written */
+  const size_t backup = (size_t)d.backup > cells ? (size_t)d.backup : cells;
   if (may_overflow)
     for (size_t q = tid; q < cells; q += kBlock)
-      R.state[cells + q] = R.state[q];
+      R.state[backup + q] = R.state[q];
   const uint64_t entries = (uint64_t)R.ncol * (uint64_t)(R.nrow + 1);
   R.use_table = entries <= (uint64_t)table_cap;
   if (R.use_table) {
@@ -487,7 +491,7 @@ __global__ void __launch_bounds__(256)
   if (overflow && may_overflow) {
     __syncthreads();
     for (size_t q = tid; q < cells; q += kBlock)
-      R.state[q] = R.state[cells + q];
+      R.state[q] = R.state[backup + q];
   }
   if (tid == 0) {
     if (!overflow)

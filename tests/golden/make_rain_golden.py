@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generator of tests/golden/digital_rain.json: the reference's own digital rain pass on recorded call sequences.
+"""Generator of tests/golden/digital_rain.json and digital_rain_edges.json: the reference's own digital rain pass on recorded
+call sequences.
 
     python3 tests/golden/make_rain_golden.py --reference <ascii-chat source tree> [--sweep-steps N]
 
@@ -10,6 +11,11 @@ no -march.  It then runs sequences of digital_rain_* calls and records, per step
 field writes before the step, the output length and SHA-256 (the full output for the hand-written strings).  Inputs are
 frames the oracle (oracle/, tests/orc.py) renders in every mode, padded, with the BLOCKS palette, rainbow-recoloured, and
 about thirty hand strings.
+
+digital_rain_edges.json holds the edge cases of tests/rain_cases.py, recorded the same way: every parameter_cases() entry
+(but those rain_cases.NOT_IN_FIXTURE names, with the reason) and the chosen boundary cases.  Their inputs are stored as
+[hex, times] parts (the run of filler lines once), never the full output, and the final grid is hashed with every NaN
+replaced by 0x7FC00000.
 
 Last, it compares the reference with tests/cabi/rain_restatement.c over a sweep (200x60 truecolor frames, several
 hundred steps with the blend) and prints how many cells and bytes differ.  Only the fixture is committed; nothing of the
@@ -31,6 +37,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 TESTS = os.path.dirname(HERE)
 sys.path.insert(0, TESTS)
 import orc  # noqa: E402
+import rain_cases as RC  # noqa: E402
 import rain_support as RS  # noqa: E402
 
 STANDINS = {
@@ -126,6 +133,32 @@ def run_case(L, name, cols, rows, steps, full):
     L.digital_rain_destroy(p)
     return {"name": name, "cols": cols, "rows": rows, "steps": rec,
             "final_grid_sha256": hashlib.sha256(np.array(grid, dtype=np.float32).tobytes()).hexdigest()}
+
+
+def run_edge_case(L, case):
+    p = L.digital_rain_init(case.cols, case.rows)
+    for op in case.ops:
+        if op[0] == "color":
+            L.digital_rain_set_color(p, *op[1:])
+        else:
+            setattr(p.contents, op[0], float(op[1]))
+    rec = []
+    for k, (frame, dt) in enumerate(zip(case.frames, case.dts)):
+        ptr = L.digital_rain_apply(p, frame, dt)
+        out = C.string_at(ptr)
+        L.free(ptr)
+        st = {"input_parts": RC.pack_frame(frame), "dt": dt, "out_len": len(out), "sha256": hashlib.sha256(out).hexdigest()}
+        if k == 0 and case.ops:
+            st["ops"] = case.ops
+        rec.append(st)
+    grid = [p.contents.previous_brightness[i] for i in range(case.cols * case.rows)]
+    L.digital_rain_destroy(p)
+    return {"name": case.name, "cols": case.cols, "rows": case.rows, "steps": rec,
+            "final_grid_sha256": hashlib.sha256(RC.canonical_grid_bytes(grid)).hexdigest()}
+
+
+def edge_cases():
+    return [c for c in RC.parameter_cases() if c.name not in RC.NOT_IN_FIXTURE] + RC.chosen_boundary_cases()
 
 
 def oracle_cases():
@@ -224,12 +257,14 @@ def main():
     ap.add_argument("--reference", required=True, help="root of the reference ascii-chat source tree")
     ap.add_argument("--sweep-steps", type=int, default=850)
     ap.add_argument("--out", default=os.path.join(HERE, "digital_rain.json"))
+    ap.add_argument("--edges-out", default=os.path.join(HERE, "digital_rain_edges.json"))
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="rain_golden_")
     try:
         L = build_reference(os.path.abspath(a.reference), tmp)
         cases = [run_case(L, n, c, r, st, False) for n, c, r, st in oracle_cases()]
         cases += [run_case(L, n, c, r, st, True) for n, c, r, st in hand_cases()]
+        edges = [run_edge_case(L, c) for c in edge_cases()]
         cells, cell_diff, byte_diff, steps_diff = sweep(L, a.sweep_steps)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
@@ -241,6 +276,15 @@ def main():
         json.dump(doc, f, indent=0, separators=(",", ":"))
         f.write("\n")
     print(f"{len(cases)} cases -> {a.out}")
+    edoc = {"about": "digital_rain_apply on the edge cases of tests/rain_cases.py (parameter extremes, tokens at the chunk "
+                     "boundary and the end of the look-ahead), recorded from the reference's own digital_rain.c "
+                     "(make_rain_golden.py).  input_parts: [hex, times] pieces of the input.  Parameter values are text for "
+                     "float().  final_grid_sha256 is taken with every NaN canonicalised to the bit pattern 0x7FC00000.",
+            "cases": edges}
+    with open(a.edges_out, "w") as f:
+        json.dump(edoc, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    print(f"{len(edges)} edge cases -> {a.edges_out}")
     print(f"sweep: {cells} cells over {a.sweep_steps} steps: {cell_diff} stored brightness values differ, "
           f"{byte_diff} output bytes differ ({steps_diff} steps)")
 

@@ -10,6 +10,7 @@ INC = os.path.join(ROOT, "include")
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 OUT_DIR = os.path.join(EMU_DIR, "_build")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "digital_rain.json")
+GOLDEN_EDGES = os.path.join(ROOT, "tests", "golden", "digital_rain_edges.json")
 TABLE_MAX = 12288
 LEN_OVERFLOW = 0xFFFFFFFF
 
@@ -29,7 +30,7 @@ class RainT(C.Structure):  # digital_rain_t
 class Desc(C.Structure):  # achip_rain_desc_t (csrc/rain.h)
     _fields_ = [("state", C.c_void_p), ("cols", C.c_void_p), ("t", C.c_float), ("fall_speed", C.c_float),
                 ("raindrop_length", C.c_float), ("decay", C.c_float), ("color", C.c_uint32), ("num_columns", C.c_int32),
-                ("num_rows", C.c_int32), ("pad", C.c_int32)]
+                ("num_rows", C.c_int32), ("backup", C.c_uint32)]
 
 
 def _fresh(out, srcs):
@@ -155,6 +156,7 @@ class Emulated:
         self.colv = np.array([[self.s.columns[c].time_offset, self.s.columns[c].speed_multiplier] for c in range(cols)],
                              dtype=np.float32).ravel()
         self.state = np.zeros(2 * cols * rows, dtype=np.float32)
+        self.backup = cols * rows  # as rain.c fills the descriptor; 0 is the kernel's default, behind the grid as written
 
     def __getattr__(self, name):  # the setters: set_color_from_filter, set_color, set_fall_speed, ...
         return getattr(self.h, name)
@@ -171,7 +173,7 @@ class Emulated:
         if s.rainbow_mode:
             s.color_r, s.color_g, s.color_b = rainbow(s.time)
         d = Desc(self.state.ctypes.data, self.colv.ctypes.data, s.time, s.fall_speed, s.raindrop_length, s.brightness_decay,
-                 s.color_r | s.color_g << 8 | s.color_b << 16 | (1 << 24 if s.first_frame else 0), s.num_columns, s.num_rows, 0)
+                 s.color_r | s.color_g << 8 | s.color_b << 16 | (1 << 24 if s.first_frame else 0), s.num_columns, s.num_rows, self.backup)
         s.first_frame = False
         return d
 
@@ -182,8 +184,9 @@ class Emulated:
         self.h.close()
 
 
-def emu_batch(items, dst_stride=None, src_stride=None):
-    """items: [(Emulated, frame bytes, dt)]; returns [bytes or LEN_OVERFLOW]."""
+def emu_batch(items, dst_stride=None, src_stride=None, src_lens=None):
+    """items: [(Emulated, frame bytes, dt)]; returns [bytes, or LEN_OVERFLOW / the error code that travelled through].
+    src_lens: the lengths the kernel is told, where they are not the frames' own."""
     import numpy as np
     n = len(items)
     if src_stride is None:
@@ -193,7 +196,7 @@ def emu_batch(items, dst_stride=None, src_stride=None):
     src = np.zeros(n * src_stride + 64, dtype=np.uint8)
     for i, (_, f, _) in enumerate(items):
         src[i * src_stride:i * src_stride + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    src_len = np.array([len(f) for _, f, _ in items], dtype=np.uint32)
+    src_len = np.array(src_lens if src_lens is not None else [len(f) for _, f, _ in items], dtype=np.uint32)
     dst = np.full(n * dst_stride + 64, 0xEE, dtype=np.uint8)
     dst_len = np.zeros(n, dtype=np.uint32)
     descs = (Desc * n)(*[ctx.desc(dt) for ctx, _, dt in items])
@@ -205,8 +208,8 @@ def emu_batch(items, dst_stride=None, src_stride=None):
     out = []
     for i in range(n):
         ln = int(dst_len[i])
-        if ln == LEN_OVERFLOW:
-            out.append(LEN_OVERFLOW)
+        if ln >= 0xFFFFFFF0:
+            out.append(ln)
         else:
             assert ln < dst_stride and dst[i * dst_stride + ln] == 0
             out.append(bytes(dst[i * dst_stride:i * dst_stride + ln]))

@@ -199,3 +199,266 @@ def test_batch_refuses_duplicate_context_and_overflows_cleanly(pkg):
     finally:
         g.close()
         ref.close()
+
+
+# ---- boundaries, parameter extremes and the host paths of rain.c (rain_cases.py; compared under its rule) ----
+import rain_cases as RC  # noqa: E402
+
+
+def _round16(n):
+    return (n + 15) // 16 * 16
+
+
+def _product(pkg, cols, rows):
+    g = pkg.Rain(cols, rows)
+    g.set_field = lambda name, v, s=g.s: setattr(s, name, v)
+    g.cells = cols * rows  # as allocated
+    return g
+
+
+def _slab(frames, stride=None):
+    """frames side by side on the device: (tensor, stride, lengths tensor)"""
+    import torch
+    stride = stride or max(16, _round16(max(len(f) for f in frames)))
+    host = np.zeros(len(frames) * stride, dtype=np.uint8)
+    for i, f in enumerate(frames):
+        host[i * stride:i * stride + len(f)] = np.frombuffer(f, dtype=np.uint8)
+    return torch.from_numpy(host).cuda(), stride, torch.tensor([len(f) for f in frames], dtype=torch.int32, device="cuda")
+
+
+def _outputs(dst, dln, stride, n):
+    """the n frames of an output slab, on the host (LEN_OVERFLOW and error codes as numbers)"""
+    lens = [int(v) & 0xFFFFFFFF for v in dln.cpu().numpy()[:n]]
+    host = dst.cpu().numpy()
+    return [ln if ln >= 0xFFFFFFF0 else bytes(host[i * stride:i * stride + ln]) for i, ln in enumerate(lens)]
+
+
+def _device_grids(pkg, ctxs, stream):
+    """the grids, as allocated, that the batches left on the device (asciichat_hip_rain_state_dev), copied out by the pack
+    kernel on the stream the batches went to"""
+    import torch
+    sizes = [4 * g.cells for g in ctxs]
+    offs = [0]
+    for s in sizes:
+        offs.append(offs[-1] + _round16(s))
+    dst = torch.zeros(offs[-1], dtype=torch.uint8, device="cuda")
+    lens = torch.tensor(sizes, dtype=torch.int32, device="cuda")
+    off = torch.zeros(2, dtype=torch.int64, device="cuda")
+    for i, g in enumerate(ctxs):
+        ptr = g.state_dev()
+        assert ptr, pkg.last_error()
+        pkg.pack_frames(ptr, _round16(sizes[i]), lens.data_ptr() + 4 * i, 1, dst.data_ptr() + offs[i], _round16(sizes[i]),
+                        off.data_ptr(), None, stream)
+    torch.cuda.synchronize()
+    host = dst.cpu().numpy()
+    return [host[offs[i]:offs[i] + sizes[i]].view(np.float32) for i in range(len(ctxs))]
+
+
+def _check_grid(got, ref, what, cols):
+    want = np.ctypeslib.as_array(ref.r.previous_brightness, shape=(ref.cols * ref.rows,))
+    a, b = np.asarray(got, dtype=np.float32).view(np.uint32), want.view(np.uint32)
+    if a.shape != b.shape or not ((a == b) | (np.isnan(got) & np.isnan(want))).all():
+        RC.check_grid(got, want, what, cols)  # names the cell
+
+
+def _run_cases_on_device(pkg, cs, per_call=256):
+    import torch
+    stream = torch.cuda.current_stream().cuda_stream
+    for lo in range(0, len(cs), per_call):
+        group = cs[lo:lo + per_call]
+        pairs = [(_product(pkg, c.cols, c.rows), RS.Restated(c.cols, c.rows)) for c in group]
+        try:
+            for (g, r), c in zip(pairs, group):
+                RC.apply_case_ops(g, c.ops)
+                RC.apply_case_ops(r, c.ops)
+            for k in range(max(len(c.frames) for c in group)):
+                live = [(p, c) for p, c in zip(pairs, group) if k < len(c.frames)]
+                src, stride, ln = _slab([c.frames[k] for _, c in live])
+                out_stride = pkg.Rain.out_stride(stride, stride)  # (no more events than bytes)
+                dst = torch.zeros(len(live) * out_stride, dtype=torch.uint8, device="cuda")
+                dln = torch.zeros(len(live), dtype=torch.int32, device="cuda")
+                rc = pkg.Rain.apply_batch([g for (g, _), _ in live], [c.dts[k] for _, c in live], src.data_ptr(), stride,
+                                          ln.data_ptr(), dst.data_ptr(), out_stride, dln.data_ptr(), stream)
+                assert rc == 0, pkg.last_error()
+                grids = _device_grids(pkg, [g for (g, _), _ in live], stream)
+                got = _outputs(dst, dln, out_stride, len(live))
+                for ((g, r), c), o, grid in zip(live, got, grids):
+                    what = f"{c.name} step {k}"
+                    assert not isinstance(o, int), f"{what}: length code 0x{o:08x}"
+                    RC.check_output(o, r.apply(c.frames[k], c.dts[k]), what)
+                    _check_grid(grid, r, what + ": grid", c.cols)
+        finally:
+            for g, r in pairs:
+                g.close()
+                r.close()
+
+
+def test_parameter_extremes_on_the_device(pkg):
+    """OCML's sin, the device's division, floorf, denormals and NaNs against glibc and SSE: bytes and bits, no tolerance"""
+    _run_cases_on_device(pkg, RC.parameter_cases())
+
+
+def test_boundary_cases_on_the_device(pkg):
+    _run_cases_on_device(pkg, RC.boundary_cases())
+
+
+def test_dropin_matches_edges_fixture(pkg):
+    import hashlib
+    fx = json.load(open(RS.GOLDEN_EDGES))
+    for case in fx["cases"]:
+        g = _product(pkg, case["cols"], case["rows"])
+        try:
+            for k, step in enumerate(case["steps"]):
+                RC.apply_case_ops(g, step.get("ops", []))
+                out = g.apply(RC.unpack_frame(step["input_parts"]), step["dt"])
+                assert (len(out), hashlib.sha256(out).hexdigest()) == (step["out_len"], step["sha256"]), f"{case['name']} step {k}"
+            assert hashlib.sha256(RC.canonical_grid_bytes(g.grid())).hexdigest() == case["final_grid_sha256"], case["name"]
+        finally:
+            g.close()
+
+
+def _small_frame(i, step):
+    E = RC.E
+    parts = [b"abcdefgh\nij", E + b"[38;2;%d;%d;9mxy" % (i % 256, (7 * i + step) % 256), "█é".encode() + b"\n\nq",
+             E + b"[48;2;1;2;3m" + E + b"[38;2;200;100;50mQ", b"z" * (i % 9) + b"\n", E + b"[5bk" + E]
+    return parts[i % 6] + parts[(i // 6 + step) % 6] + parts[(i + 2 * step) % 6]
+
+
+def test_batch_longer_than_a_ring_segment(pkg):
+    """2 200 frames in one call: three launches from three ring segments"""
+    import torch
+    n = 2200
+    stream = torch.cuda.current_stream().cuda_stream
+    pairs = [(_product(pkg, 8, 3), RS.Restated(8, 3)) for _ in range(n)]
+    try:
+        for step in range(2):
+            frames = [_small_frame(i, step) for i in range(n)]
+            dts = [0.01 + 0.0001 * (i % 97) for i in range(n)]
+            src, stride, ln = _slab(frames)
+            out_stride = pkg.Rain.out_stride(stride, stride)
+            dst = torch.zeros(n * out_stride, dtype=torch.uint8, device="cuda")
+            dln = torch.zeros(n, dtype=torch.int32, device="cuda")
+            rc = pkg.Rain.apply_batch([g for g, _ in pairs], dts, src.data_ptr(), stride, ln.data_ptr(), dst.data_ptr(), out_stride,
+                                      dln.data_ptr(), stream)
+            assert rc == 0, pkg.last_error()
+            grids = _device_grids(pkg, [g for g, _ in pairs], stream)
+            for i, ((g, r), o) in enumerate(zip(pairs, _outputs(dst, dln, out_stride, n))):
+                RC.check_output(o, r.apply(frames[i], dts[i]), f"step {step} frame {i}")
+                _check_grid(grids[i], r, f"step {step} frame {i}: grid", 8)
+    finally:
+        for g, r in pairs:
+            g.close()
+            r.close()
+
+
+def _issue_rounds(pkg, pairs, rounds, streams, grid):
+    """`rounds` batch calls over the same contexts with no host wait between them, call j on streams[j % len(streams)];
+    each call has its own input and output slab, all inputs on the device before the first call.  Returns what to check
+    after the caller's synchronise: [(dst, dln, out_stride, frames, dts)]."""
+    import torch
+    n = len(pairs)
+    calls = []
+    for j in range(rounds):
+        frames = [_small_frame(i + 5 * j, j) * (1 + (i + j) % 3) for i in range(n)]
+        src, stride, ln = _slab(frames)
+        out_stride = pkg.Rain.out_stride(stride, stride)
+        calls.append((src, stride, ln, torch.zeros(n * out_stride, dtype=torch.uint8, device="cuda"),
+                      torch.zeros(n, dtype=torch.int32, device="cuda"), out_stride, frames, [0.01 + 0.002 * ((i + j) % 5) for i in range(n)]))
+    torch.cuda.synchronize()  # every slab is written before any stream starts: the calls order the contexts, not these
+    for j, (src, stride, ln, dst, dln, out_stride, frames, dts) in enumerate(calls):
+        rc = pkg.Rain.apply_batch([g for g, _ in pairs], dts, src.data_ptr(), stride, ln.data_ptr(), dst.data_ptr(), out_stride,
+                                  dln.data_ptr(), streams[j % len(streams)])
+        assert rc == 0, pkg.last_error()
+    return calls
+
+
+def _check_rounds(pairs, calls, what):
+    for j, (src, stride, ln, dst, dln, out_stride, frames, dts) in enumerate(calls):
+        for i, ((g, r), o) in enumerate(zip(pairs, _outputs(dst, dln, out_stride, len(pairs)))):
+            RC.check_output(o, r.apply(frames[i], dts[i]), f"{what}: call {j} frame {i}")
+
+
+def test_forty_calls_without_a_host_wait_wrap_the_ring(pkg):
+    """16 ring segments, 40 calls over the same 32 contexts: the ring wraps twice and every call blends with the one before"""
+    import torch
+    stream = torch.cuda.current_stream().cuda_stream
+    pairs = [(_product(pkg, 12, 5), RS.Restated(12, 5)) for _ in range(32)]
+    try:
+        calls = _issue_rounds(pkg, pairs, 40, [stream], (12, 5))
+        torch.cuda.synchronize()
+        _check_rounds(pairs, calls, "one stream")
+        for i, grid in enumerate(_device_grids(pkg, [g for g, _ in pairs], stream)):
+            _check_grid(grid, pairs[i][1], f"context {i}: grid after 40 calls", 12)
+    finally:
+        for g, r in pairs:
+            g.close()
+            r.close()
+
+
+def test_two_streams_in_turn_then_the_dropin_without_a_host_wait(pkg):
+    import torch
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    pairs = [(_product(pkg, 12, 5), RS.Restated(12, 5)) for _ in range(32)]
+    try:
+        calls = _issue_rounds(pkg, pairs, 12, [s1.cuda_stream, s2.cuda_stream], (12, 5))
+        # the drop-in directly behind batch calls that are still in flight: its own stream waits for the context's last launch
+        f = RC.PARAM_FRAME
+        outs = [g.apply(f, 0.02) for g, _ in pairs]
+        torch.cuda.synchronize()
+        _check_rounds(pairs, calls, "two streams")
+        for i, (g, r) in enumerate(pairs):
+            RC.check_output(outs[i], r.apply(f, 0.02), f"context {i}: drop-in behind the batches")
+            _check_grid(np.array(g.grid(), dtype=np.float32), r, f"context {i}: grid after the drop-in", 12)
+    finally:
+        for g, r in pairs:
+            g.close()
+            r.close()
+
+
+def test_dropin_staging_grows_and_is_reused(pkg):
+    g, r = _product(pkg, 40, 12), RS.Restated(40, 12)
+    small = RC.E + b"[38;2;1;2;3mab\ncd" + RC.E + b"[48;2;9;9;m"
+    line = RC.E + b"[38;2;200;100;50m" + b"abcdefghijklmnopqrstuvwxyz0123456789#@%&" + RC.E + b"[48;2;5;6;7m+\n"
+    big = line * (200 * 1024 // len(line) + 1)
+    assert len(small) == 30 and len(big) >= 200 * 1024
+    try:
+        for k, (f, dt) in enumerate(((small, 0.02), (big, 0.03), (small, 0.04), (big, 0.01))):
+            RC.check_output(g.apply(f, dt), r.apply(f, dt), f"step {k} ({len(f)} bytes)")
+            _check_grid(np.array(g.grid(), dtype=np.float32), r, f"step {k}: grid", 40)
+    finally:
+        g.close()
+        r.close()
+
+
+def test_grid_written_smaller_than_allocated_and_back_on_the_device(pkg):
+    """the sequence of test_rain_boundaries.py through the product's context: batch calls, the overflow step in a slot too
+    small, the grid as allocated read from the device after every step, and the drop-in at the end"""
+    import torch
+    SHRUNK_FRAME, SHRUNK_STEPS = RC.SHRUNK_FRAME, RC.SHRUNK_STEPS
+    stream = torch.cuda.current_stream().cuda_stream
+    g, r = _product(pkg, 12, 6), RS.Restated(12, 6)
+    src, stride, ln = _slab([SHRUNK_FRAME])
+    out_stride = pkg.Rain.out_stride(stride, stride)
+    dst = torch.zeros(out_stride, dtype=torch.uint8, device="cuda")
+    dln = torch.zeros(1, dtype=torch.int32, device="cuda")
+    try:
+        for k, (cols, rows, dt, overflow) in enumerate(SHRUNK_STEPS):
+            if cols:
+                for o in (g.s, r.r):
+                    o.num_columns, o.num_rows = cols, rows
+            rc = pkg.Rain.apply_batch([g], [dt], src.data_ptr(), stride, ln.data_ptr(), dst.data_ptr(), 256 if overflow else out_stride,
+                                      dln.data_ptr(), stream)
+            assert rc == 0, pkg.last_error()
+            grid = _device_grids(pkg, [g], stream)[0]
+            got = _outputs(dst, dln, out_stride, 1)[0]
+            if overflow:
+                assert got == RS.LEN_OVERFLOW
+                r.r.time = g.s.time
+            else:
+                RC.check_output(got, r.apply(SHRUNK_FRAME, dt), f"step {k}")
+            _check_grid(grid, r, f"step {k}: the grid as allocated", None)
+        RC.check_output(g.apply(SHRUNK_FRAME, 0.02), r.apply(SHRUNK_FRAME, 0.02), "drop-in at the end")
+        _check_grid(np.array(g.grid(), dtype=np.float32), r, "drop-in at the end: grid", 12)
+    finally:
+        g.close()
+        r.close()
