@@ -450,6 +450,86 @@ class Rain:
             self.p = None
 
 
+def _bind_box(L):
+    vp, ci, sz = C.c_void_p, C.c_int, C.c_size_t
+    if getattr(L, "_box_bound", False):
+        return L
+    for name, res, args in (("asciichat_hip_box_create", ci, [C.POINTER(vp), C.POINTER(Frame), ci]),
+                            ("asciichat_hip_box_update", ci, [vp, C.POINTER(Frame), vp]),
+                            ("asciichat_hip_box_image_pitch", sz, [vp]),
+                            ("asciichat_hip_box_run", ci, [vp, vp, sz, vp]),
+                            ("asciichat_hip_box_get_uniform", ci, [vp]),
+                            ("asciichat_hip_box_render_frames", ci, [vp, vp, sz, C.POINTER(Frame)]),
+                            ("asciichat_hip_box_destroy", None, [vp]),
+                            ("asciichat_hip_box_downscale", ci, [vp, ci, ci, ci, vp, ci, ci, ci, ci, vp])):
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    L._box_bound = True
+    return L
+
+
+class Box:
+    """The opt-in area-average downscale in front of a plan (asciichat_hip_box_*): every source frame averaged to the image
+    its render descriptor would have point-sampled.  Not a parity mode -- the reference point-samples; the render of the
+    averaged image is what matches the reference's renderer over that image.  Use: Box(frames), render_frames(images),
+    Plan(mode, palette, those); per tick update(), run(), plan.render() on one stream."""
+
+    def __init__(self, frames):
+        self.L = _bind_box(lib())
+        self.n = len(frames)
+        self._arr = (Frame * self.n)(*frames)
+        self._h = C.c_void_p()
+        rc = self.L.asciichat_hip_box_create(C.byref(self._h), self._arr, self.n)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_hip_box_create failed ({rc}): {last_error()}")
+        self.pitch = int(self.L.asciichat_hip_box_image_pitch(self._h))
+
+    @property
+    def uniform(self):
+        """True when launches pass the batch's common descriptor in the kernel arguments"""
+        return bool(self.L.asciichat_hip_box_get_uniform(self._h))
+
+    def update(self, frames, stream=0):
+        self._arr = frames if isinstance(frames, C.Array) else (Frame * self.n)(*frames)
+        rc = self.L.asciichat_hip_box_update(self._h, self._arr, stream)
+        if rc != 0:
+            raise RuntimeError(f"box_update failed ({rc}): {last_error()}")
+        self.pitch = int(self.L.asciichat_hip_box_image_pitch(self._h))
+
+    def run(self, images_ptr, pitch=None, stream=0):
+        rc = self.L.asciichat_hip_box_run(self._h, images_ptr, self.pitch if pitch is None else pitch, stream)
+        if rc != 0:
+            raise RuntimeError(f"box_run failed ({rc}): {last_error()}")
+
+    def render_frames(self, images_ptr, pitch=None):
+        """the descriptors a plan renders the averaged images with"""
+        out = (Frame * self.n)()
+        rc = self.L.asciichat_hip_box_render_frames(self._h, images_ptr, self.pitch if pitch is None else pitch, out)
+        if rc != 0:
+            raise RuntimeError(f"box_render_frames failed ({rc}): {last_error()}")
+        return list(out)
+
+    def close(self):
+        if self._h:
+            self.L.asciichat_hip_box_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def box_downscale(src_ptr, src_w, src_h, dst_ptr, dst_w, dst_h, src_stride=0, flip_x=False, flip_y=False, stream=0):
+    """asciichat_hip_box_downscale: one image averaged to dst_w x dst_h (3 * dst_w * dst_h bytes at dst_ptr); asynchronous"""
+    rc = _bind_box(lib()).asciichat_hip_box_downscale(src_ptr, src_w, src_h, src_stride, dst_ptr, dst_w, dst_h, int(flip_x),
+                                                      int(flip_y), stream)
+    if rc != 0:
+        raise RuntimeError(f"box_downscale failed ({rc}): {last_error()}")
+
+
 def last_error():
     return lib().asciichat_hip_last_error().decode("utf-8", "replace")
 

@@ -215,6 +215,12 @@ int achip_frame_set_dither_style(achip_frame_t *f, bool use_background, bool ram
 
 uint32_t achip_nn_ratio(int src, int dst) { return (uint32_t)((((uint64_t)src << 16) / (uint64_t)dst) + 1u); }
 
+void achip_box_bounds(int src, int out, int i, int *lo, int *hi) {
+  const int64_t a = (int64_t)i * src / out, b = (int64_t)(i + 1) * src / out;
+  *lo = (int)a;
+  *hi = (int)(b > a + 1 ? b : a + 1);
+}
+
 int achip_frame_identity(achip_frame_t *f, const uint8_t *src_dev, int w, int h) {
   if (!f || w <= 0 || h <= 0)
     return -1;

@@ -63,6 +63,12 @@ int achip_frame_set_rainbow(achip_frame_t *f, float time_seconds);
 /* 16.16 nearest-neighbour ratio, image.c:293-294 */
 uint32_t achip_nn_ratio(int src, int dst);
 
+/* The box of output index i (0 <= i < out) on an axis of `src` pixels averaged to `out`, for the opt-in area-average
+ * downscale (asciichat_hip_box_*): lo = floor(i * src / out), hi = max(lo + 1, floor((i + 1) * src / out)) -- source indices
+ * lo .. hi - 1; one pixel where the axis is upscaled.  The floor partition is not mirror-symmetric: flips apply to the
+ * averaged image, not to the source. */
+void achip_box_bounds(int src, int out, int i, int *lo, int *hi);
+
 /* Upper bound (bytes, excluding the NUL) of one rendered frame; multiple of 16 when rounded by the caller. */
 size_t achip_out_bound(int mode, const achip_frame_t *f);
 

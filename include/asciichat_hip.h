@@ -164,6 +164,43 @@ int asciichat_hip_set_coalesce_min_callers(int n);
 int asciichat_hip_resize(const uint8_t *src_dev, int src_w, int src_h, uint8_t *dst_dev, int dst_w, int dst_h,
                          void *stream);
 
+/*
+ * Opt-in area-average (box filter) downscale in front of the renderers.  NOT a parity mode: the reference point-samples its
+ * source (image.c:293-325), this pass averages.  Its result is not byte-identical to the reference for the same source
+ * frame; it is byte-identical to the reference's renderer run over the averaged image.  The drop-in layer never uses it.
+ *
+ * Integer and exact.  For a descriptor with source src_w x src_h and sampled size out_w x out_h (pixel rows: half-block
+ * modes are already doubled by achip_frame_setup), the column box of x is x0 = floor(x * src_w / out_w),
+ * x1 = max(x0 + 1, floor((x + 1) * src_w / out_w)), rows alike (achip_box_bounds, achip_host.h); per channel
+ * A[y][x] = (S + n / 2) / n with S the sum over the box and n its pixels.  The ACHIP_OP_FLIP_X / _Y bits of `ops` mirror the
+ * averaged image: stored pixel (x, y) = A[fy ? out_h - 1 - y : y][fx ? out_w - 1 - x : x].  Tints, the foreground override,
+ * dither bits and padding stay in the descriptor for the render.  Sources of 1..3840 x 1..2160 at any alignment and any
+ * src_stride >= 3 * src_w (0 = tight), averaged sizes up to 16384 a side.  comp != NULL: ASCIICHAT_HIP_ERR_NOT_SUPPORTED; a
+ * NULL source, non-positive or oversize dimensions, a short stride: ASCIICHAT_HIP_ERR_INVALID_PARAM.
+ *
+ * box_create(frames) takes the tick's render descriptors as achip_frame_setup() made them (host array; src device-visible);
+ * box_update the next tick's (same n; in stream order with box_run; a refused or failed update leaves the box as it was).
+ * box_create's descriptors are on the device when it returns: the first box_run may go to any stream.  box_run writes
+ * image i to images_dev + i * pitch (3 * out_w * out_h bytes of the slot, nothing else; pitch >= the largest image,
+ * box_image_pitch() rounds that up to 128); asynchronous.  box_render_frames: frames_out[i] = frames[i] rewritten onto images_dev + i * pitch -- src_w x src_h =
+ * out_w x out_h, ratios 65537, tight stride, flip bits cleared, comp NULL; pad_left / pad_top and every other bit of ops
+ * kept: descriptors achip_choose_geometry cannot tell from achip_frame_identity()'s.  Use: box_create, box_render_frames,
+ * plan_create(mode, palette, frames_out); per tick box_update, box_run, plan_render on one stream.
+ * box_get_uniform: 1 when the batch's common descriptor travels in the kernel arguments (equal geometry, constant pitch).
+ * box_downscale: one image, beside asciichat_hip_resize (dst_dev holds 3 * dst_w * dst_h bytes).
+ */
+typedef struct asciichat_hip_box asciichat_hip_box_t;
+int asciichat_hip_box_create(asciichat_hip_box_t **box, const achip_frame_t *frames, int n_frames);
+int asciichat_hip_box_update(asciichat_hip_box_t *box, const achip_frame_t *frames, void *stream);
+size_t asciichat_hip_box_image_pitch(const asciichat_hip_box_t *box);
+int asciichat_hip_box_run(asciichat_hip_box_t *box, uint8_t *images_dev, size_t pitch, void *stream);
+int asciichat_hip_box_get_uniform(const asciichat_hip_box_t *box);
+int asciichat_hip_box_render_frames(const asciichat_hip_box_t *box, const uint8_t *images_dev, size_t pitch,
+                                    achip_frame_t *frames_out);
+void asciichat_hip_box_destroy(asciichat_hip_box_t *box);
+int asciichat_hip_box_downscale(const uint8_t *src_dev, int src_w, int src_h, int src_stride, uint8_t *dst_dev, int dst_w,
+                                int dst_h, int flip_x, int flip_y, void *stream);
+
 /* Materialise the W x 2H pixel-space grid composite (src/server/stream.c:664-779) on device.
  * comp_host is filled by achip_composite_setup(); dst_dev holds canvas_w*canvas_h*3 bytes. */
 int asciichat_hip_composite(const achip_composite_t *comp_host, uint8_t *dst_dev, void *stream);

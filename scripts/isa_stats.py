@@ -10,6 +10,7 @@ Extracts the device code objects from the built library, reads every kernel's AM
     has stopped being cheap;
   * render_stream_kernel: <= 64 VGPRs (two 1024-thread or four 512-thread workgroups per CU; the truecolor-background
     mode, whose 48-byte tokens fill the LDS first, <= 72) and no scratch memory (SGPRs parked in VGPR lanes are fine);
+  * box_kernel: <= 128 VGPRs (several 4-wave workgroups per CU keep its loads in flight) and no scratch;
   * rain_kernel: <= 256 VGPRs (two 4-wave workgroups per CU, what its LDS allows) and no scratch;
   * every other kernel: no VGPR spills.
 
@@ -137,6 +138,9 @@ def main():
         elif "rain_kernel" in name:  # one 4-wave workgroup per frame with up to 57 KB of LDS: two per CU at most
             short = "achip::rain::rain_kernel"
             limit, why = 256, "2 waves per SIMD: the two workgroups per CU its LDS allows"
+        elif "box_kernel" in name:  # 4-wave workgroups with up to 45 KB of LDS: three per CU at the widest source
+            short = "achip::box::box_kernel"
+            limit, why = 128, "4 waves per SIMD: what the LDS stage of a 1080p source allows and more than a 4K one does"
         else:
             short = demangle(name).split("(")[0].replace("void ", "")[-70:]
         problems = []
