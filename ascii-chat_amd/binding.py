@@ -652,6 +652,15 @@ class Plan:
         if rc != 0:
             raise RuntimeError(f"plan_render_packets_packed failed ({rc}): {last_error()}")
 
+    def render_packets_zpacked(self, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity,
+                               off_ptr, len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+        """render + the wire stage with the frames compressed for the wire (asciichat_hip_plan_render_packets_zpacked)"""
+        rc = _bind_zpack(lib()).asciichat_hip_plan_render_packets_zpacked(self._h, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr,
+                                                                          hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                                                                          len_out_ptr, scratch_ptr, scratch_bytes, stream)
+        if rc != 0:
+            raise RuntimeError(f"plan_render_packets_zpacked failed ({rc}): {last_error()}")
+
     def set_fused_crc(self, mode):
         """-1 automatic (fused where it is the faster form), 0 never, 1 wherever the geometry carries it"""
         rc = lib().asciichat_hip_plan_set_fused_crc(self._h, mode)
@@ -740,6 +749,37 @@ def pack_frames(slab_ptr, stride, len_ptr, n, dst_ptr, dst_capacity, off_ptr=Non
     rc = lib().asciichat_hip_pack_frames(slab_ptr, stride, len_ptr, n, dst_ptr, dst_capacity, off_ptr, len_out_ptr, stream)
     if rc != 0:
         raise RuntimeError(f"pack_frames failed ({rc}): {last_error()}")
+
+
+def _bind_zpack(L):
+    vp, ci, sz, u32 = C.c_void_p, C.c_int, C.c_size_t, C.c_uint32
+    if getattr(L, "_zpack_bound", False):
+        return L
+    for name, res, args in (("asciichat_hip_zpack_scratch_bytes", sz, [u32, ci]),
+                            ("asciichat_hip_frame_packets_zpacked", ci, [vp, sz, vp, u32, ci, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+                            ("asciichat_hip_plan_render_packets_zpacked", ci, [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz,
+                                                                               vp])):
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    L._zpack_bound = True
+    return L
+
+
+def zpack_scratch_bytes(max_len, n):
+    """bytes of device scratch a zpacked call over n frames of up to max_len bytes needs"""
+    return int(_bind_zpack(lib()).asciichat_hip_zpack_scratch_bytes(max_len, n))
+
+
+def frame_packets_zpacked(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                          len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+    """asciichat_hip_frame_packets_zpacked: the wire stage with the frames compressed on the device where the sender's rule
+    says so (zstd frames of raw / RLE / Huffman-literals blocks), pack_frames' layout over the sent lengths; asynchronous"""
+    rc = _bind_zpack(lib()).asciichat_hip_frame_packets_zpacked(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr,
+                                                                dst_ptr, dst_capacity, off_ptr, len_out_ptr, scratch_ptr, scratch_bytes,
+                                                                stream)
+    if rc != 0:
+        raise RuntimeError(f"frame_packets_zpacked failed ({rc}): {last_error()}")
 
 
 class HostBuffer:

@@ -68,6 +68,10 @@ void achip_sample_set_free(achip_sample_set_t *S);
 size_t achip_sample_set_block_bytes(const achip_sample_set_t *S);
 void achip_sample_set_pack(const achip_sample_set_t *S, const uint8_t *pixels, uint8_t *blk);
 
+/* plan.c: frames of a plan (0 for NULL) */
+struct asciichat_hip_plan;
+int achip_plan_frame_count(const struct asciichat_hip_plan *plan);
+
 /* buffer_pool.c: device alias of a pointer inside a pinned pool block, or NULL */
 const void *achip_pool_device_ptr(const void *host_ptr);
 

@@ -810,6 +810,9 @@ int asciichat_hip_plan_render_packets_packed(asciichat_hip_plan_t *p, uint8_t *s
   return rc;
 }
 
+/* frames of the plan (zpack.c's plan_render_packets_zpacked: the plan itself is private to this file); 0 for no plan */
+int achip_plan_frame_count(const asciichat_hip_plan_t *p) { return p ? p->n : 0; }
+
 /* diagnostics: the same launch with the per-wave timestamps of plan_render_profiled */
 int asciichat_hip_plan_render_crc_profiled(asciichat_hip_plan_t *p, uint8_t *out_dev, size_t out_stride,
                                            uint32_t *out_len_dev, uint32_t *crc_out_dev,

@@ -1,0 +1,66 @@
+/* zpack.h -- the "zhuf" wire pass: the scratch layout shared by its four kernels (zpack_kernels.hpp), and the
+ * launcher (zpack.hip) between them and the host side (zpack.c).  Not installed. */
+#ifndef ACHIP_ZPACK_H
+#define ACHIP_ZPACK_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define ACHIP_ZPACK_BLOCK 256
+#define ACHIP_ZPACK_PIECE 131072u /* bytes of a frame per zstd block */
+#define ACHIP_ZPACK_MAX_BITS 11
+#define ACHIP_ZPACK_MIN_HUF 17u   /* no compressed block is below 16 bytes: shorter pieces never gain */
+
+/* one record per (frame, piece), then one per frame; 32-bit words */
+#define ACHIP_ZPACK_REC_WORDS 160
+#define ACHIP_ZPACK_FRM_WORDS 8
+enum {
+  ZR_KIND = 0,   /* block type: 0 raw, 1 RLE, 2 compressed; 3: the frame has no such piece */
+  ZR_N = 1,      /* bytes of the piece */
+  ZR_BODY = 2,   /* bytes of the block behind its 3-byte header */
+  ZR_CRC = 3,    /* CRC register after the piece's bytes: from 0xFFFFFFFF for piece 0, from 0 for the others */
+  ZR_STREAM = 4, /* 4 words: bytes of the four Huffman streams */
+  ZR_MAXBITS = 8,
+  ZR_TOP = 9,    /* the largest symbol present (its weight is implied) */
+  ZR_RLE = 10,   /* the byte of an RLE block */
+  ZR_CSIZE = 11, /* Compressed_Size of the literals section */
+  ZR_FMT = 12,   /* its Size_Format: 1, 2, 3 */
+  ZR_AT = 13,    /* where the block starts in the zhuf frame (piece 0: 0, the frame header travels with it) */
+  ZR_BCRC = 14,  /* CRC register (from 0) over the block as sent */
+  ZR_BLEN = 15,  /* ... and its bytes */
+  ZR_TABLE = 16  /* 129 words: code | length << 16 */
+};
+enum {
+  ZF_KIND = 0, /* 0: sent as it is, 1: sent as a zhuf frame, 2: a render error code */
+  ZF_SENT = 1,
+  ZF_OFF_LO = 2,
+  ZF_OFF_HI = 3,
+  ZF_FITS = 4,
+  ZF_STATE = 5, /* CRC register after the original frame (from 0xFFFFFFFF) */
+  ZF_PIECES = 6,
+  ZF_LEN = 7 /* the original length (0 for an error code) */
+};
+
+static inline uint32_t achip_zpack_pieces(uint32_t max_len) {
+  return max_len <= ACHIP_ZPACK_PIECE ? 1u : (uint32_t)(((uint64_t)max_len + ACHIP_ZPACK_PIECE - 1u) / ACHIP_ZPACK_PIECE);
+}
+static inline size_t achip_zpack_scratch_bytes(uint32_t max_len, int n) {
+  if (n <= 0)
+    return 0;
+  return 4u * (size_t)n * ((size_t)achip_zpack_pieces(max_len) * ACHIP_ZPACK_REC_WORDS + ACHIP_ZPACK_FRM_WORDS);
+}
+
+/* frames i < n at base + i * stride, len_dev[i] bytes each (<= max_len): see asciichat_hip_frame_packets_zpacked.  Returns a
+ * hipError_t. */
+int achip_launch_zpack(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
+                       uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
+                       uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -314,6 +314,25 @@ int asciichat_hip_frame_packets_packed(const uint8_t *base_dev, size_t stride, c
                                        const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
                                        uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                        uint32_t *len_out, void *stream);
+/* ... and with the frames COMPRESSED on the device for the wire ("zhuf"): every frame is measured as a zstd
+ * frame of raw, RLE and Huffman-literals blocks with zero sequences -- any libzstd decodes it, the reference's clients as
+ * they are (lib/network/compression.c:58-70) -- and goes out in that form when the reference sender's own rule says so
+ * (lib/network/packet/packet.c:444-469: more than 1024 bytes, and 5 * compressed < 4 * original), else as it is:
+ *   hdr_out_dev      {width, height, original_size = len, compressed_size = bytes sent | 0, checksum, flags = 0x02 | 0};
+ *                    checksum is always the CRC-32C of the ORIGINAL bytes (what the client checks after decoding)
+ *   packet_crc_out_dev[i]  CRC-32C of header || payload AS SENT
+ *   dst / off_out / len_out  pack_frames' layout over the SENT lengths: off_out[i] = sum over j < i of round16(len_out[j]),
+ *                    off_out[n] = bytes used, in frame order (no first-come claim); len_dev keeps the original lengths.
+ *                    A frame whose length is a render error code takes no room (len_out carries the code).
+ * scratch_dev: device memory of asciichat_hip_zpack_scratch_bytes(max_len, n) bytes, 8-byte aligned, the call's own until
+ * the work has run (calls in flight on different streams need different blocks).  Asynchronous, four launches on `stream`.
+ * Only pieces whose bytes are all <= 0x80 are Huffman-coded (the tree travels in zstd's direct 4-bit form): half-block
+ * frames and multi-byte palettes go out as they are.  No plan and no drop-in call chooses this form by itself. */
+size_t asciichat_hip_zpack_scratch_bytes(uint32_t max_len, int n);
+int asciichat_hip_frame_packets_zpacked(const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len, int n,
+                                        const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
+                                        uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
+                                        uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream);
 
 /*
  * Compacted output (SURVEY.md 8e "prefer gathering compacted per-rank buffers ... lengths first").  A render leaves frame
@@ -468,6 +487,14 @@ int asciichat_hip_plan_render_packets_packed(asciichat_hip_plan_t *plan, uint8_t
                                              uint32_t *out_len_dev, const uint32_t *dims_dev, uint32_t *crc_out_dev,
                                              uint8_t *hdr_out_dev, uint32_t *packet_crc_out_dev, uint8_t *dst,
                                              size_t dst_capacity, uint64_t *off_out, uint32_t *len_out, void *stream);
+/* plan_render + asciichat_hip_frame_packets_zpacked (the frames compressed for the wire where the sender's rule says so) on
+ * the same stream; scratch_dev: asciichat_hip_zpack_scratch_bytes(out_stride, frames of the plan) bytes.  Always this form's
+ * two steps: the plan's own choices among the packed forms do not apply, and no plan takes this form unasked. */
+int asciichat_hip_plan_render_packets_zpacked(asciichat_hip_plan_t *plan, uint8_t *slab_dev, size_t out_stride,
+                                              uint32_t *out_len_dev, const uint32_t *dims_dev, uint32_t *crc_out_dev,
+                                              uint8_t *hdr_out_dev, uint32_t *packet_crc_out_dev, uint8_t *dst,
+                                              size_t dst_capacity, uint64_t *off_out, uint32_t *len_out, void *scratch_dev,
+                                              size_t scratch_bytes, void *stream);
 /* Exact-length frames beyond the 48 KB of the one-launch form above: LENGTH-FIRST -- the stream kernel's loop run twice,
  * lengths first, then the emission at the place the frame claimed (whole-frame plans of truecolor foreground with an all-ASCII
  * palette; ASCIICHAT_HIP_ERR_NOT_SUPPORTED otherwise).  Frames land in completion order (off_out[i], 16-byte aligned;

@@ -12,6 +12,8 @@ Extracts the device code objects from the built library, reads every kernel's AM
     mode, whose 48-byte tokens fill the LDS first, <= 72) and no scratch memory (SGPRs parked in VGPR lanes are fine);
   * box_kernel: <= 128 VGPRs (several 4-wave workgroups per CU keep its loads in flight) and no scratch;
   * rain_kernel: <= 256 VGPRs (two 4-wave workgroups per CU, what its LDS allows) and no scratch;
+  * zpack_measure_kernel / zpack_encode_kernel: <= 128 VGPRs (four waves per SIMD: the four 4-wave workgroups per CU a 36 KB
+    frame's LDS image allows) and no scratch;
   * every other kernel: no VGPR spills.
 
 Usage: isa_stats.py [path/to/libasciichat_hip.so] [--out profiles/isa_stats.txt]   (exit status 1 on a violation)
@@ -141,6 +143,9 @@ def main():
         elif "box_kernel" in name:  # 4-wave workgroups with up to 45 KB of LDS: three per CU at the widest source
             short = "achip::box::box_kernel"
             limit, why = 128, "4 waves per SIMD: what the LDS stage of a 1080p source allows and more than a 4K one does"
+        elif "zpack_measure_kernel" in name or "zpack_encode_kernel" in name:  # 4-wave workgroups, LDS by the frame length
+            short = demangle(name).split("(")[0].replace("void ", "")[-70:]
+            limit, why = 128, "4 waves per SIMD: up to four workgroups per CU at 80x24 truecolor frames"
         else:
             short = demangle(name).split("(")[0].replace("void ", "")[-70:]
         problems = []

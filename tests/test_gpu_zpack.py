@@ -1,0 +1,197 @@
+"""The zhuf wire pass on the GPU through the C ABI: the batch of tests/zpack_support.py against the restatement byte for byte
+(destination in device memory and in mapped host memory), every sent frame decoded back by tests/zhuf_ref.py's decoder and by
+libzstd where it loads, headers as the reference's receiver checks them, two calls back to back on one stream, frames of two
+and three pieces, and plan_render_packets_zpacked over real renders."""
+import os
+import struct
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import orc  # noqa: E402
+import zhuf_ref as Z  # noqa: E402
+import zpack_support as ZS  # noqa: E402
+
+CASES = ZS.small_cases()
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from __graft_entry__ import load_package
+
+    p = load_package()
+    assert torch.cuda.is_available() and p.lib().asciichat_hip_device_count() > 0
+    return p
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+class _Call:
+    """the buffers of one call; dst in device memory or in mapped host memory"""
+
+    def __init__(self, pkg, frames, dims, capacity=None, host=False, tail=256):
+        import torch
+        self.pkg, self.frames, self.dims, self.n = pkg, frames, dims, len(frames)
+        slab, self.stride, ln, self.mx = ZS.slab_of(frames)
+        self.slab = torch.from_numpy(np.concatenate([slab, np.full(16, ZS.FILL, dtype=np.uint8)])).cuda()
+        self.len = torch.from_numpy(ln.view(np.int32)).cuda()
+        self.len_before = ln
+        _, total = ZS.expect(frames, dims)
+        self.cap = total if capacity is None else capacity
+        self.nbytes = max(self.cap, total) + tail
+        self.host = pkg.HostBuffer(self.nbytes) if host else None
+        if host:
+            self.host.view()[:] = ZS.FILL
+            self.dst_ptr = self.host.dev
+        else:
+            self.dst = torch.full((self.nbytes,), ZS.FILL, dtype=torch.uint8, device="cuda")
+            self.dst_ptr = self.dst.data_ptr()
+        n = self.n
+        self.off = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
+        self.len_out = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+        self.crc = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+        self.pkt = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+        self.hdr = torch.full((24 * n,), ZS.FILL, dtype=torch.uint8, device="cuda")
+        self.d = torch.from_numpy(np.array(dims, dtype=np.uint32).reshape(n, 2).view(np.int32)).cuda()
+        self.sbytes = pkg.zpack_scratch_bytes(self.mx, n)
+        self.scratch = torch.zeros(self.sbytes // 8 + 1, dtype=torch.int64, device="cuda")
+
+    def launch(self, stream):
+        self.pkg.frame_packets_zpacked(self.slab.data_ptr(), self.stride, self.len.data_ptr(), self.mx, self.n, self.d.data_ptr(),
+                                       self.crc.data_ptr(), self.hdr.data_ptr(), self.pkt.data_ptr(), self.dst_ptr, self.cap,
+                                       self.off.data_ptr(), self.len_out.data_ptr(), self.scratch.data_ptr(), self.sbytes, stream)
+
+    def check(self, what):
+        dst = self.host.view().copy() if self.host else self.dst.cpu().numpy()
+        out = dict(dst=dst, off=self.off.cpu().numpy().view(np.uint64), len_out=self.len_out.cpu().numpy().view(np.uint32),
+                   crc=self.crc.cpu().numpy().view(np.uint32), hdr=self.hdr.cpu().numpy(), pkt=self.pkt.cpu().numpy().view(np.uint32))
+        ZS.check(self.frames, self.dims, out, self.cap, what)
+        assert np.array_equal(self.len.cpu().numpy().view(np.uint32), self.len_before), "len_dev keeps the original lengths"
+        if self.host:
+            self.host.close()
+
+
+@pytest.mark.parametrize("host", [False, True], ids=["device", "mapped host"])
+def test_mixed_batch_equals_the_restatement(pkg, host):
+    import torch
+    frames = list(CASES.values())
+    c = _Call(pkg, frames, ZS.dims_of(len(frames)), host=host)
+    c.launch(_stream())
+    torch.cuda.synchronize()
+    c.check("mixed")
+
+
+def test_tight_capacity(pkg):
+    import torch
+    frames = [CASES[k] for k in ("1025 skewed", "error code", "one byte value (RLE)", "1024 skewed (as it is: the size floor)",
+                                 "two byte values", "5 bytes")]
+    dims = ZS.dims_of(len(frames))
+    _, total = ZS.expect(frames, dims)
+    for short in (1, 17, 700):
+        c = _Call(pkg, frames, dims, capacity=total - short)
+        c.launch(_stream())
+        torch.cuda.synchronize()
+        c.check(f"capacity -{short}")
+
+
+def test_two_calls_back_to_back_on_one_stream(pkg):
+    """no host wait in between: each call has its own scratch and outputs, both complete"""
+    import torch
+    a = [CASES[k] for k in ("truecolor 20x6", "fibonacci counts (limiter and repair)", "error code", "all 129 symbols")]
+    b = [CASES[k] for k in ("two byte values", "S = 128", "empty", "uniform below 0x80 (as it is: the ratio)", "1027 skewed")]
+    ca, cb = _Call(pkg, a, ZS.dims_of(len(a))), _Call(pkg, b, ZS.dims_of(len(b)))
+    s = _stream()
+    ca.launch(s)
+    cb.launch(s)
+    torch.cuda.synchronize()
+    ca.check("first call")
+    cb.check("second call")
+
+
+@pytest.mark.parametrize("n", [131073, 262145])
+def test_large_pieces_once_each(pkg, n):
+    """two and three pieces, the last one a single byte; next to it a frame whose second block is raw inside a zhuf frame"""
+    import torch
+    frames = [ZS.skewed(n, 20 + n % 7)]
+    if n == 131073:
+        frames.append(ZS.skewed(131072, 21) + ZS.uniform7(100, 22))
+    c = _Call(pkg, frames, ZS.dims_of(len(frames)))
+    c.launch(_stream())
+    torch.cuda.synchronize()
+    c.check(f"{n} bytes")
+
+
+def test_a_full_size_truecolor_frame_in_256_copies(pkg):
+    """80x24 truecolor cells (about 11 KB a frame, 256 workgroups in flight): one expectation, shared"""
+    import torch
+    f = ZS.ansi_truecolor(80, 24, 30)
+    assert ZS.wire_of(f)[2] == Z.FLAG_COMPRESSED
+    c = _Call(pkg, [f] * 256, [(80, 24)] * 256)
+    c.launch(_stream())
+    torch.cuda.synchronize()
+    c.check("256 equal frames")
+
+
+def _source(w, h, seed):
+    img = orc.frame_smooth(w, h)
+    img[h // 4:h // 2, w // 4:w // 2] = orc.frame_hash_noise(w // 2 - w // 4, h // 2 - h // 4, seed)
+    return img
+
+
+@pytest.mark.parametrize("mode,caps,n", [(1, (3, 0), 12), (5, (3, 2), 4)], ids=["truecolor fg x12", "half-block x4"])
+def test_plan_render_packets_zpacked(pkg, mode, caps, n):
+    """12 frames of 160x90 -> 80x24 truecolor compress (sent < original is all that is asked of the ratio); 4 half-block
+    frames hold bytes above 0x80 and go out as they are, flags 0.  Either way the payload decodes to the oracle's frame."""
+    import torch
+    cl, rm = caps
+    imgs = [_source(160, 90, 40 + i) for i in range(n)]
+    dev = torch.from_numpy(np.stack(imgs)).cuda()
+    fs = [pkg.frame_setup(dev.data_ptr() + i * 160 * 90 * 3, 160, 90, 80, 24, rm, False, False, False) for i in range(n)]
+    plan = pkg.Plan(mode, orc.PALETTE_STANDARD, fs)
+    stride = plan.stride
+    slab = torch.zeros(n * stride, dtype=torch.uint8, device="cuda")
+    ln = torch.zeros(n, dtype=torch.int32, device="cuda")
+    cap = n * stride
+    host = pkg.HostBuffer(cap)
+    off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    len_out = torch.zeros(n, dtype=torch.int32, device="cuda")
+    crc = torch.zeros(n, dtype=torch.int32, device="cuda")
+    pkt = torch.zeros(n, dtype=torch.int32, device="cuda")
+    hdr = torch.zeros(24 * n, dtype=torch.uint8, device="cuda")
+    d = torch.from_numpy(np.array([(80, 24)] * n, dtype=np.uint32).view(np.int32)).cuda()
+    sbytes = pkg.zpack_scratch_bytes(stride, n)
+    scratch = torch.zeros(sbytes // 8 + 1, dtype=torch.int64, device="cuda")
+    plan.render_packets_zpacked(slab.data_ptr(), stride, ln.data_ptr(), d.data_ptr(), crc.data_ptr(), hdr.data_ptr(), pkt.data_ptr(),
+                                host.dev, cap, off.data_ptr(), len_out.data_ptr(), scratch.data_ptr(), sbytes, _stream())
+    torch.cuda.synchronize()
+    dst = host.view().copy()
+    offs, sent, orig = off.cpu().numpy(), len_out.cpu().numpy().view(np.uint32), ln.cpu().numpy().view(np.uint32)
+    hdrs, pkts = hdr.cpu().numpy(), pkt.cpu().numpy().view(np.uint32)
+    at = 0
+    for i in range(n):
+        exp = orc.convert_with_caps(imgs[i], 80, 24, cl, rm, False, False, False)
+        assert int(orig[i]) == len(exp) and int(offs[i]) == at
+        payload = dst[at:at + int(sent[i])].tobytes()
+        w_, h_, osz, csz, cks, flags = struct.unpack(">6I", hdrs[24 * i:24 * i + 24].tobytes())
+        assert (w_, h_, osz, cks) == (80, 24, len(exp), orc.crc32c(exp))
+        assert int(pkts[i]) == orc.crc32c(hdrs[24 * i:24 * i + 24].tobytes() + payload)
+        if mode == 1:
+            assert int(sent[i]) < len(exp) and flags == Z.FLAG_COMPRESSED and csz == int(sent[i])
+            assert payload == ZS.wire_of(exp)[0] and Z.decode(payload) == exp
+            if Z.libzstd() is not None:
+                assert Z.zstd_decompress(payload, len(exp)) == exp
+        else:
+            assert flags == 0 and csz == 0 and payload == exp
+        at += (int(sent[i]) + 15) // 16 * 16
+    assert int(offs[n]) == at
+    plan.close()
+    host.close()
