@@ -11,7 +11,16 @@ extern "C" {
 #endif
 
 #define ACHIP_ZPACK_BLOCK 256
+#ifndef ACHIP_ZPACK_PIECE /* (only the second emulator library of the tests defines it, smaller: tests/zpack_support.py) */
 #define ACHIP_ZPACK_PIECE 131072u /* bytes of a frame per zstd block */
+#endif
+#ifdef __cplusplus
+static_assert(ACHIP_ZPACK_PIECE % 16u == 0u && ACHIP_ZPACK_PIECE >= 16u, "blocks start a piece apart in the slab: whole 16-byte groups");
+static_assert(ACHIP_ZPACK_PIECE <= 131072u, "Block_Maximum_Size");
+#else
+_Static_assert(ACHIP_ZPACK_PIECE % 16u == 0u && ACHIP_ZPACK_PIECE >= 16u, "blocks start a piece apart in the slab: whole 16-byte groups");
+_Static_assert(ACHIP_ZPACK_PIECE <= 131072u, "Block_Maximum_Size");
+#endif
 #define ACHIP_ZPACK_MAX_BITS 11
 #define ACHIP_ZPACK_MIN_HUF 17u   /* no compressed block is below 16 bytes: shorter pieces never gain */
 

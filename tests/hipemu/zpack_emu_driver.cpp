@@ -14,6 +14,8 @@ static const uint4 *crc_tab_256() {
   return reinterpret_cast<const uint4 *>(t);
 }
 
+extern "C" uint32_t emu_zpack_piece() { return ACHIP_ZPACK_PIECE; }
+
 extern "C" size_t emu_zpack_scratch_bytes(uint32_t max_len, int n) { return achip_zpack_scratch_bytes(max_len, n); }
 
 extern "C" void emu_zpack(const uint8_t *base, uint64_t stride, const uint32_t *len, uint32_t max_len, int n, const uint32_t *dims,

@@ -1,7 +1,9 @@
 """The zhuf wire pass on the GPU through the C ABI: the batch of tests/zpack_support.py against the restatement byte for byte
 (destination in device memory and in mapped host memory), every sent frame decoded back by tests/zhuf_ref.py's decoder and by
 libzstd where it loads, headers as the reference's receiver checks them, two calls back to back on one stream, frames of two
-and three pieces, and plan_render_packets_zpacked over real renders."""
+and three pieces, plan_render_packets_zpacked over real renders, and every family of tests/zpack_cases.py -- the pass at
+its block, stream and batch boundaries -- at the real piece size, a few batches per test.  Out of scope: offsets above 4 GB
+(ZF_OFF_HI), which would have to move more than 4 GB, and lengths above max_len, which the caller promises."""
 import os
 import struct
 import sys
@@ -14,6 +16,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import orc  # noqa: E402
 import zhuf_ref as Z  # noqa: E402
+import zpack_cases as ZC  # noqa: E402
 import zpack_support as ZS  # noqa: E402
 
 CASES = ZS.small_cases()
@@ -38,10 +41,10 @@ def _stream():
 class _Call:
     """the buffers of one call; dst in device memory or in mapped host memory"""
 
-    def __init__(self, pkg, frames, dims, capacity=None, host=False, tail=256):
+    def __init__(self, pkg, frames, dims, capacity=None, host=False, tail=256, stride=None):
         import torch
         self.pkg, self.frames, self.dims, self.n = pkg, frames, dims, len(frames)
-        slab, self.stride, ln, self.mx = ZS.slab_of(frames)
+        slab, self.stride, ln, self.mx = ZS.slab_of(frames, stride)
         self.slab = torch.from_numpy(np.concatenate([slab, np.full(16, ZS.FILL, dtype=np.uint8)])).cuda()
         self.len = torch.from_numpy(ln.view(np.int32)).cuda()
         self.len_before = ln
@@ -195,3 +198,68 @@ def test_plan_render_packets_zpacked(pkg, mode, caps, n):
     assert int(offs[n]) == at
     plan.close()
     host.close()
+
+
+# ---- the boundaries of tests/zpack_cases.py ----------------------------------------------------------------------------
+def _once(pkg, frames, what, **kw):
+    import torch
+    c = _Call(pkg, frames, ZS.dims_of(len(frames)), **kw)
+    c.launch(_stream())
+    torch.cuda.synchronize()
+    records = dict(scratch=c.scratch.cpu().numpy().view(np.uint32), pieces=max(1, -(-c.mx // Z.PIECE)))
+    c.check(what)
+    return records
+
+
+def test_tail_lengths_gains_and_symbols_behind_a_full_piece(pkg):
+    """(a), (b), (c): one batch of carrier + tail frames, the carrier's block coded and decoded once"""
+    named = ZC.tail_lengths(Z.PIECE) + ZC.tail_lengths_long() + ZC.tail_gain(Z.PIECE) + ZC.tail_symbols(Z.PIECE)
+    _once(pkg, [f for _, f in named], "tails")
+
+
+@pytest.mark.parametrize("host", [False, True], ids=["device", "mapped host"])
+def test_tail_blocks_at_every_phase(pkg, host):
+    """(d): a Huffman block at each of the 16 phases of a group, raw and RLE blocks at 0 / 1 / 8 / 15, three pieces"""
+    _once(pkg, [f for _, f in ZC.tail_phases(Z.PIECE)], "phases", host=host)
+
+
+def test_ratio_stream_cuts_and_lane_shares(pkg):
+    """(e), (f), (g) in one batch of 235 frames"""
+    named = ZC.ratio_frames() + ZC.stream_cut_frames() + ZC.chunk_step_frames()
+    _once(pkg, [f for _, f in named], "whole frames")
+
+
+def test_histogram_frames_and_the_table_in_the_scratch_records(pkg):
+    """(h): the payloads, and the table the measure kernel left"""
+    hists = ZC.histograms()
+    rec = _once(pkg, [f for _, _, f in hists], "histograms")
+    for i, (name, hist, _) in enumerate(hists):
+        lens = Z.code_lengths(hist)
+        codes, max_bits = Z.canonical_codes(lens)
+        table, dev_bits = ZS.device_table(rec, i)
+        assert dev_bits == max_bits, (name, dev_bits, max_bits)
+        assert table == [c | (d << 16) if d else 0 for c, d in zip(codes, lens)], name
+
+
+@pytest.mark.parametrize("host", [False, True], ids=["device", "mapped host"])
+def test_more_frames_than_threads_of_the_plan(pkg, host):
+    """(i): 257 and 600 short frames, then 600 with a capacity that ends inside a frame of index >= 256"""
+    for n in (257, 600):
+        _once(pkg, ZC.short_batch(n), f"{n} frames", host=host)
+    frames = ZC.short_batch(600)
+    i, tight = ZC.capacity_inside(frames, ZS.dims_of(600), 256, ZS.expect)
+    assert i >= 256
+    _once(pkg, frames, f"600 frames, capacity inside frame {i}", host=host, capacity=tight)
+
+
+@pytest.mark.parametrize("host", [False, True], ids=["device", "mapped host"])
+def test_short_frames_among_frames_of_whole_pieces(pkg, host):
+    """(i): an empty frame, an error code and 5 bytes in front of frames of 1, 2 and 3 pieces; capacities that end inside
+    the first and the second block of the first frame of several pieces; a stride 48 bytes wider; one piece alone"""
+    frames = ZC.piece_batch(Z.PIECE)
+    dims = ZS.dims_of(len(frames))
+    _once(pkg, frames, "whole pieces", host=host)
+    for tight in ZC.piece_batch_capacities(frames, dims, ZS.expect, Z.PIECE):
+        _once(pkg, frames, f"capacity {tight}", host=host, capacity=tight)
+    _once(pkg, frames, "stride + 48", host=host, stride=ZS.slab_of(frames)[1] + 48)
+    _once(pkg, [frames[3]], "one piece alone", host=host)

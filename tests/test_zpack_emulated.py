@@ -96,7 +96,8 @@ def test_library_refuses_before_it_needs_a_device_and_needs_one_after():
 
 def test_frames_of_two_and_three_pieces():
     """131 073 bytes (the last piece one byte: an RLE block), 131 072 + 100 uniform bytes (a raw block inside a zhuf frame) and
-    262 145 bytes: block offsets at every phase of a 16-byte group, checksums combined over the pieces"""
+    262 145 bytes: blocks behind the first start at three phases of a 16-byte group (every phase: test_zpack_boundaries.py),
+    checksums combined over the pieces"""
     frames = [ZS.skewed(131073, 20), ZS.skewed(131072, 21) + ZS.uniform7(100, 22), ZS.skewed(262145, 23, spread=0.3)]
     for f in frames[:2]:
         assert ZS.wire_of(f)[2] == Z.FLAG_COMPRESSED

@@ -1,7 +1,9 @@
 """The "zhuf" wire form restated in Python: a zstd frame built only from raw, RLE and Huffman-literals
 blocks with zero sequences.  encode() is what the device must produce byte for byte (the length algorithm included);
 decode() is a decoder of exactly this subset, written from the format and not by inverting encode(); zstd_decompress() is
-libzstd's own decoder where libzstd.so.1 loads.  TESTS ONLY."""
+libzstd's own decoder where libzstd.so.1 loads.  encode(), decode() and wire() take the piece size (the product's by default:
+the tests' second emulator library has a smaller one); a piece of 1 KB or more is coded once and its block decoded once,
+however many frames hold it.  TESTS ONLY."""
 import ctypes as C
 import struct
 
@@ -15,9 +17,10 @@ RATIO_NUM, RATIO_DEN, MIN_SIZE = 4, 5, 1024  # COMPRESSION_RATIO_THRESHOLD 0.8, 
 
 
 # ---- code lengths ------------------------------------------------------------------------------------------------------
-def code_lengths(hist):
+def code_lengths(hist, steps=None):
     """hist: 129 counts (symbols 0..128), at least two of them non-zero -> 129 code lengths (0: symbol absent), every
-    length <= MAX_BITS, Kraft sum exactly 1.  Integer only, deterministic."""
+    length <= MAX_BITS, Kraft sum exactly 1.  Integer only, deterministic.  steps: a dict that receives how often the
+    limiter demoted and promoted ("demoted", "promoted": 0 where the tree was no deeper than MAX_BITS)."""
     leaves = sorted((c, s) for s, c in enumerate(hist) if c)  # count ascending, then symbol ascending
     m = len(leaves)
     assert m >= 2
@@ -40,6 +43,7 @@ def code_lengths(hist):
     for k in range(2 * m - 3, -1, -1):
         depth[k] = depth[parent[k]] + 1
     lens = depth[:m]
+    demoted = promoted = 0
     if max(lens) > MAX_BITS:
         lens = [min(d, MAX_BITS) for d in lens]
         full = 1 << MAX_BITS
@@ -51,12 +55,16 @@ def code_lengths(hist):
                     best = j
             lens[best] += 1
             kraft -= full >> lens[best]
+            demoted += 1
         while kraft < full:  # promote: the most frequent symbol whose step fits what is missing
             for j in range(m - 1, -1, -1):
                 if (full >> lens[j]) <= full - kraft:
                     kraft += full >> lens[j]
                     lens[j] -= 1
+                    promoted += 1
                     break
+    if steps is not None:
+        steps["demoted"], steps["promoted"] = demoted, promoted
     out = [0] * 129
     for (_, s), d in zip(leaves, lens):
         out[s] = d
@@ -107,8 +115,14 @@ def _block_header(last, kind, size):
 
 def huf_block_body(piece, tables=None):
     """the compressed block of a piece (literals section + the zero sequence count), or None when the piece is not coded"""
+    body = huf_block_candidate(piece, tables)
+    return body if body is not None and len(body) < len(piece) else None
+
+
+def huf_block_candidate(piece, tables=None):
+    """the compressed block of a piece whether it gains or not; None where no table is built at all"""
     n = len(piece)
-    if n < MIN_HUF_PIECE or max(piece) > 0x80:
+    if n < MIN_HUF_PIECE or max(piece) > 0x80 or piece.count(piece[0]) == n:
         return None
     hist = [0] * 129
     for b in piece:
@@ -130,33 +144,61 @@ def huf_block_body(piece, tables=None):
         if n < (1 << bits) and csize < (1 << bits):
             break
     head = (2 | (fmt << 2) | (n << 4) | (csize << (4 + bits))).to_bytes(2 + fmt, "little")
-    body = head + tree + struct.pack("<HHH", *(len(s) for s in streams[:3])) + b"".join(streams) + b"\x00"
-    return body if len(body) < n else None
+    return head + tree + struct.pack("<HHH", *(len(s) for s in streams[:3])) + b"".join(streams) + b"\x00"
 
 
-def encode(frame, tables=None):
-    """the zhuf frame of `frame` (any length); tables: a list that receives the code lengths of every coded piece"""
+_bodies = {}  # piece -> (its compressed block or None, its code lengths or None): long pieces are coded once
+
+
+def _body_of(piece, tables):
+    if len(piece) < 1024:
+        return huf_block_body(piece, tables)
+    if piece not in _bodies:
+        t = []
+        body = huf_block_body(piece, t)
+        _bodies[piece] = (body, t[0] if t else None)
+    body, lens = _bodies[piece]
+    if tables is not None and lens is not None:
+        tables.append(lens)
+    return body
+
+
+def encode(frame, tables=None, piece=PIECE):
+    """the zhuf frame of `frame` (any length), one block per `piece` bytes; tables: a list that receives the code lengths
+    of every coded piece"""
     frame = bytes(frame)
     out = [MAGIC, bytes([FHD]), struct.pack("<I", len(frame))]
-    pieces = [frame[k:k + PIECE] for k in range(0, len(frame), PIECE)] or [b""]
-    for k, piece in enumerate(pieces):
+    pieces = [frame[k:k + piece] for k in range(0, len(frame), piece)] or [b""]
+    for k, part in enumerate(pieces):
         last = k == len(pieces) - 1
-        n = len(piece)
-        if n and piece.count(piece[0]) == n:
-            out += [_block_header(last, 1, n), piece[:1]]
+        n = len(part)
+        if n and part.count(part[0]) == n:
+            out += [_block_header(last, 1, n), part[:1]]
             continue
-        body = huf_block_body(piece, tables)
+        body = _body_of(part, tables)
         if body is None:
-            out += [_block_header(last, 0, n), piece]
+            out += [_block_header(last, 0, n), part]
         else:
             out += [_block_header(last, 2, len(body)), body]
     return b"".join(out)
 
 
-def wire(frame):
+def blocks(z):
+    """[(type, size, offset of the block's header in the frame)] of a zhuf frame"""
+    at, out, last = 9, [], False
+    while not last:
+        h = int.from_bytes(z[at:at + 3], "little")
+        last, kind, size = bool(h & 1), (h >> 1) & 3, h >> 3
+        out.append((kind, size, at))
+        at += 3 + (1 if kind == 1 else size)
+    assert at == len(z)
+    return out
+
+
+def wire(frame, piece=PIECE):
     """the frame rule of the sender: -> (payload as sent, compressed_size, flags)"""
     frame = bytes(frame)
-    z = encode(frame)
+    z = encode(frame, piece=piece)
     if len(frame) <= MIN_SIZE or RATIO_DEN * len(z) >= RATIO_NUM * len(frame):
         return frame, 0, 0
     return z, len(z), FLAG_COMPRESSED
@@ -180,14 +222,16 @@ def _need(cond, what):
 def _decode_stream(data, n_sym, table, max_bits):
     """one Huffman bitstream read backwards from its end mark; table: 2^max_bits entries of (symbol, length)"""
     _need(len(data) >= 1 and data[-1] != 0, "stream without an end mark")
-    value = int.from_bytes(data, "little")
-    pos = value.bit_length() - 1  # the end mark; the bits below it are the codes, first symbol on top
+    digits = bin(int.from_bytes(data, "little"))[3:]  # behind "0b" and the end mark: the codes, the first symbol's first
+    pos = len(digits)  # bits left
+    digits += "0" * max_bits
+    at = 0
     out = bytearray()
     for _ in range(n_sym):
-        window = (value >> (pos - max_bits)) if pos >= max_bits else (value << (max_bits - pos))
-        sym, ln = table[window & ((1 << max_bits) - 1)]
+        sym, ln = table[int(digits[at:at + max_bits], 2)]
         _need(ln <= pos, "stream runs out of bits")
         pos -= ln
+        at += ln
         out.append(sym)
     _need(pos == 0, "stream has bits left over")
     return bytes(out)
@@ -241,7 +285,18 @@ def _decode_literals(body):
     return out
 
 
-def decode(payload):
+_literals = {}  # compressed block -> its literals: long blocks are decoded once
+
+
+def _literals_of(body):
+    if len(body) < 1024:
+        return _decode_literals(body)
+    if body not in _literals:
+        _literals[body] = _decode_literals(body)
+    return _literals[body]
+
+
+def decode(payload, piece=PIECE):
     payload = bytes(payload)
     _need(payload[:4] == MAGIC and len(payload) >= 9 and payload[4] == FHD, "frame header")
     size = struct.unpack("<I", payload[5:9])[0]
@@ -253,11 +308,11 @@ def decode(payload):
         last, kind, bsize = bool(h & 1), (h >> 1) & 3, h >> 3
         _need(kind != 3, "reserved block type")
         take = 1 if kind == 1 else bsize
-        _need(at + take <= len(payload) and bsize <= PIECE, "block beyond the frame")
+        _need(at + take <= len(payload) and bsize <= piece, "block beyond the frame")
         body = payload[at:at + take]
         at += take
-        out.append(body if kind == 0 else body * bsize if kind == 1 else _decode_literals(body))
-        _need(len(out[-1]) <= PIECE, "block regenerates more than 128 KB")
+        out.append(body if kind == 0 else body * bsize if kind == 1 else _literals_of(body))
+        _need(len(out[-1]) <= piece, "block regenerates more than a piece")
     _need(at == len(payload), "bytes behind the last block")
     res = b"".join(out)
     _need(len(res) == size, "Frame_Content_Size")

@@ -82,21 +82,21 @@ def small_cases():
 _wire = {}
 
 
-def wire_of(frame):
-    """zhuf_ref.wire(frame), computed once per distinct frame"""
-    if frame not in _wire:
-        _wire[frame] = Z.wire(frame)
-    return _wire[frame]
+def wire_of(frame, piece=Z.PIECE):
+    """zhuf_ref.wire(frame), computed once per distinct frame (and piece size)"""
+    if (frame, piece) not in _wire:
+        _wire[frame, piece] = Z.wire(frame, piece)
+    return _wire[frame, piece]
 
 
-def expect(frames, dims):
+def expect(frames, dims, piece=Z.PIECE):
     """-> per frame dict(sent, payload, hdr, crc, pkt, off), total"""
     res, off = [], 0
     for f, (w, h) in zip(frames, dims):
         if isinstance(f, int):
             res.append(dict(sent=0, len_out=f, payload=b"", hdr=bytes(24), crc=0, pkt=0, off=off, flags=0))
             continue
-        payload, csz, flags = wire_of(f)
+        payload, csz, flags = wire_of(f, piece)
         crc = orc.crc32c(f)
         hdr = Z.packet_header(w, h, len(f), csz, crc, flags)
         res.append(dict(sent=len(payload), len_out=len(payload), payload=payload, hdr=hdr, crc=crc, pkt=orc.crc32c(hdr + payload),
@@ -105,9 +105,9 @@ def expect(frames, dims):
     return res, off
 
 
-def check(frames, dims, out, capacity, what=""):
+def check(frames, dims, out, capacity, what="", piece=Z.PIECE):
     """out: dict(dst, off, len_out, crc, hdr, pkt) of numpy arrays (dst at least `capacity` bytes, FILL before the call)"""
-    exp, total = expect(frames, dims)
+    exp, total = expect(frames, dims, piece)
     n = len(frames)
     assert int(out["off"][n]) == total, (what, int(out["off"][n]), total)
     written = np.zeros(len(out["dst"]), dtype=bool)
@@ -131,7 +131,7 @@ def check(frames, dims, out, capacity, what=""):
         got = out["dst"][e["off"]:e["off"] + e["sent"]].tobytes()
         assert got == e["payload"], (tag, "payload differs at", next(k for k in range(len(got)) if got[k] != e["payload"][k]))
         if flags:
-            assert Z.decode(got) == f, tag
+            assert Z.decode(got, piece) == f, tag
             if Z.libzstd() is not None:
                 assert Z.zstd_decompress(got, len(f)) == f, tag
             written[e["off"]:e["off"] + e["sent"]] = True  # a zhuf frame is stored to the byte
@@ -158,20 +158,21 @@ def dims_of(n):
 
 
 # ---- the emulator ------------------------------------------------------------------------------------------------------
-_emu = None
+_emu = {}
 
 
-def emulator():
-    global _emu
-    if _emu is None:
+def emulator(piece=Z.PIECE):
+    """the emulator library; a piece size other than the product's gives a second library built with that ACHIP_ZPACK_PIECE"""
+    if piece not in _emu:
         drv = os.path.join(EMU_DIR, "zpack_emu_driver.cpp")
         srcs = [drv, os.path.join(EMU_DIR, "hip_emu.h"), os.path.join(EMU_DIR, "gfx950_ops.hpp")] + \
                [os.path.join(CSRC, f) for f in ("zpack_kernels.hpp", "zpack.h", "crc_math.hpp", "render_kernels.hpp")]
-        so = os.path.join(OUT_DIR, "libzpack_emu.so")
+        so = os.path.join(OUT_DIR, "libzpack_emu.so" if piece == Z.PIECE else "libzpack_emu_%d.so" % piece)
+        define = [] if piece == Z.PIECE else ["-DACHIP_ZPACK_PIECE=%du" % piece]
         if not (os.path.exists(so) and all(os.path.getmtime(s) <= os.path.getmtime(so) for s in srcs)):
             os.makedirs(OUT_DIR, exist_ok=True)
             tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-I" + EMU_DIR, "-I" + CSRC, "-I" + INC, drv, "-o", tmp])
+            subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-I" + EMU_DIR, "-I" + CSRC, "-I" + INC] + define + [drv, "-o", tmp])
             os.replace(tmp, so)
         L = C.CDLL(so)
         vp = C.c_void_p
@@ -179,8 +180,10 @@ def emulator():
         L.emu_zpack_scratch_bytes.argtypes = [C.c_uint32, C.c_int]
         L.emu_zpack.restype = None
         L.emu_zpack.argtypes = [vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
-        _emu = L
-    return _emu
+        L.emu_zpack_piece.restype = C.c_uint32
+        assert L.emu_zpack_piece() == piece
+        _emu[piece] = L
+    return _emu[piece]
 
 
 def _aligned(nbytes, fill):
@@ -189,14 +192,14 @@ def _aligned(nbytes, fill):
     return raw[o:o + nbytes]
 
 
-def emu_run(frames, dims, capacity=None, tail=256):
-    """the four kernels over the frames -> (out dict for check(), capacity)"""
-    L = emulator()
+def emu_run(frames, dims, capacity=None, tail=256, piece=Z.PIECE, stride=None):
+    """the four kernels over the frames -> (out dict for check() and the scratch records, capacity)"""
+    L = emulator(piece)
     n = len(frames)
-    slab0, stride, ln, mx = slab_of(frames)
+    slab0, stride, ln, mx = slab_of(frames, stride)
     slab = _aligned(len(slab0) + 16, FILL)
     slab[:len(slab0)] = slab0
-    _, total = expect(frames, dims)
+    _, total = expect(frames, dims, piece)
     cap = total if capacity is None else capacity
     dst = _aligned(max(cap, total) + tail, FILL)
     off = np.full(n + 1, 0xEEEEEEEE, dtype=np.uint64)
@@ -208,4 +211,14 @@ def emu_run(frames, dims, capacity=None, tail=256):
     scratch = np.full(L.emu_zpack_scratch_bytes(mx, n) // 4, 0xEEEEEEEE, dtype=np.uint32)
     L.emu_zpack(slab.ctypes.data, stride, ln.ctypes.data, mx, n, d.ctypes.data, crc.ctypes.data, hdr.ctypes.data, pkt.ctypes.data,
                 dst.ctypes.data, cap, off.ctypes.data, len_out.ctypes.data, scratch.ctypes.data)
-    return dict(dst=dst, off=off, len_out=len_out, crc=crc, hdr=hdr, pkt=pkt), cap
+    return dict(dst=dst, off=off, len_out=len_out, crc=crc, hdr=hdr, pkt=pkt, scratch=scratch, pieces=max(1, -(-mx // piece))), cap
+
+
+# ---- the scratch records (csrc/zpack.h) --------------------------------------------------------------------------------
+REC_WORDS, ZR_KIND, ZR_N, ZR_MAXBITS, ZR_TABLE = 160, 0, 1, 8, 16
+
+
+def device_table(out, i, p=0):
+    """-> (129 words code | length << 16, maxBits) that measure left for piece p of frame i"""
+    rec = out["scratch"][(i * out["pieces"] + p) * REC_WORDS:][:REC_WORDS]
+    return [int(x) for x in rec[ZR_TABLE:ZR_TABLE + 129]], int(rec[ZR_MAXBITS])
