@@ -60,8 +60,12 @@ def one_launch(request):
     emu.lib().emu_set_crc_one_launch(0)
 
 
-@pytest.mark.parametrize("force", [None, (3, 6), (2, 16), (70, 1), (130, 1)],
-                         ids=["launcher", "3x6", "2x16", "70x1", "130x1"])
+# "launcher" is emu_crc32c's OWN choice, which restates an older launcher: 64 KB spans always, one workgroup only up to
+# 128 KB.  The product (achip_crc_parts) also cuts 16 KB spans and keeps many buffers above 128 KB in one workgroup; its three
+# geometries for these frames (70001 bytes at the most) are forced below: one workgroup, five spans of 16 KB, and two of
+# 64 KB -- the "2x16" that was here already.  tests/test_crc_boundaries.py runs them at their boundaries.
+@pytest.mark.parametrize("force", [None, (3, 6), (2, 16), (70, 1), (130, 1), (1, 0), (5, 4)],
+                         ids=["launcher", "3x6", "2x16", "70x1", "130x1", "product one workgroup", "product 5x16K"])
 def test_crc_and_packet_headers_emulated(force, one_launch):
     frames, dims = _frames()
     crc, hdr, pkt = emu.crc32c_frames(frames, dims, force=force)

@@ -12,6 +12,7 @@ sys.path.insert(0, ROOT)
 
 import emu  # noqa: E402
 import orc  # noqa: E402
+from crc_ref import packed_reference  # noqa: E402  (the packed layout: shared with the checksum pass's boundary suite)
 
 
 def ops_for(flip_x, flip_y, flt, w=10, h=10):
@@ -92,17 +93,6 @@ def test_tint_and_flip_kernels_gpu():
 
 
 # ---- compaction of a rendered slab ("compacted per-rank buffers, lengths first") ------------------------------
-def packed_reference(slab, stride, lens):
-    """off[i] = sum_{j<i} round16(len_ok[j]); frame i's bytes at off[i]"""
-    off, out = [], bytearray()
-    for i, l in enumerate(lens):
-        l = 0 if l >= 0xFFFFFFF0 else int(l)
-        off.append(len(out))
-        out += slab[i * stride:i * stride + l].tobytes()
-        out += bytes((-l) % 16)
-    return off + [len(out)], bytes(out)
-
-
 def test_pack_frames_kernel_emulated():
     rng = np.random.default_rng(5)
     for n, stride, slices in ((1, 64, 1), (5, 256, 1), (37, 1024, 3), (300, 128, 2), (3, 16384, 4)):
