@@ -87,6 +87,9 @@ class _OlderBuild:
         try:
             return getattr(self._L, name)
         except AttributeError:
+            if name.startswith("_"):  # a flag the binding keeps on the library (_zpack_bound, ...), not an entry point
+                raise
+
             def missing(*a, **k):
                 raise RuntimeError(f"{LIB_PATH} has no {name}")
             object.__setattr__(self, name, missing)
@@ -661,6 +664,15 @@ class Plan:
         if rc != 0:
             raise RuntimeError(f"plan_render_packets_zpacked failed ({rc}): {last_error()}")
 
+    def render_packets_zpacked_wide(self, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity,
+                                    off_ptr, len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+        """render + the wide form of that stage (asciichat_hip_plan_render_packets_zpacked_wide; zpack_wide_scratch_bytes)"""
+        rc = _bind_zpack(lib()).asciichat_hip_plan_render_packets_zpacked_wide(self._h, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr,
+                                                                               hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                                                                               len_out_ptr, scratch_ptr, scratch_bytes, stream)
+        if rc != 0:
+            raise RuntimeError(f"plan_render_packets_zpacked_wide failed ({rc}): {last_error()}")
+
     def set_fused_crc(self, mode):
         """-1 automatic (fused where it is the faster form), 0 never, 1 wherever the geometry carries it"""
         rc = lib().asciichat_hip_plan_set_fused_crc(self._h, mode)
@@ -755,13 +767,14 @@ def _bind_zpack(L):
     vp, ci, sz, u32 = C.c_void_p, C.c_int, C.c_size_t, C.c_uint32
     if getattr(L, "_zpack_bound", False):
         return L
-    for name, res, args in (("asciichat_hip_zpack_scratch_bytes", sz, [u32, ci]),
-                            ("asciichat_hip_frame_packets_zpacked", ci, [vp, sz, vp, u32, ci, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
-                            ("asciichat_hip_plan_render_packets_zpacked", ci, [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz,
-                                                                               vp])):
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
+    for name, res, args in (("asciichat_hip_zpack%s_scratch_bytes", sz, [u32, ci]),
+                            ("asciichat_hip_frame_packets_zpacked%s", ci, [vp, sz, vp, u32, ci, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+                            ("asciichat_hip_plan_render_packets_zpacked%s", ci, [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz,
+                                                                                 vp])):
+        for form in ("", "_wide"):
+            fn = getattr(L, name % form)
+            fn.restype = res
+            fn.argtypes = args
     L._zpack_bound = True
     return L
 
@@ -780,6 +793,22 @@ def frame_packets_zpacked(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_p
                                                                 stream)
     if rc != 0:
         raise RuntimeError(f"frame_packets_zpacked failed ({rc}): {last_error()}")
+
+
+def zpack_wide_scratch_bytes(max_len, n):
+    """bytes of device scratch a zpacked_wide call over n frames of up to max_len bytes needs"""
+    return int(_bind_zpack(lib()).asciichat_hip_zpack_wide_scratch_bytes(max_len, n))
+
+
+def frame_packets_zpacked_wide(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                               len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+    """asciichat_hip_frame_packets_zpacked_wide: frame_packets_zpacked over all 256 byte values (half-block frames and
+    multi-byte palettes are coded too: the tree in zstd's FSE-compressed form); scratch of zpack_wide_scratch_bytes"""
+    rc = _bind_zpack(lib()).asciichat_hip_frame_packets_zpacked_wide(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr,
+                                                                     pkt_ptr, dst_ptr, dst_capacity, off_ptr, len_out_ptr, scratch_ptr,
+                                                                     scratch_bytes, stream)
+    if rc != 0:
+        raise RuntimeError(f"frame_packets_zpacked_wide failed ({rc}): {last_error()}")
 
 
 class HostBuffer:

@@ -43,6 +43,12 @@ enum {
   ZR_BLEN = 15,  /* ... and its bytes */
   ZR_TABLE = 16  /* 129 words: code | length << 16 */
 };
+/* the wide form's record: the words above with a table of 256 entries, then the tree as it is sent */
+#define ACHIP_ZPACK_WIDE_REC_WORDS 320
+enum {
+  ZWR_TREELEN = 272, /* bytes of the tree description in the literals section, its header byte included (either form) */
+  ZWR_TREE = 276     /* 32 words: the FSE form's bytes, header byte first (largest symbol above 128 only) */
+};
 enum {
   ZF_KIND = 0, /* 0: sent as it is, 1: sent as a zhuf frame, 2: a render error code */
   ZF_SENT = 1,
@@ -63,11 +69,21 @@ static inline size_t achip_zpack_scratch_bytes(uint32_t max_len, int n) {
   return 4u * (size_t)n * ((size_t)achip_zpack_pieces(max_len) * ACHIP_ZPACK_REC_WORDS + ACHIP_ZPACK_FRM_WORDS);
 }
 
+static inline size_t achip_zpack_wide_scratch_bytes(uint32_t max_len, int n) {
+  if (n <= 0)
+    return 0;
+  return 4u * (size_t)n * ((size_t)achip_zpack_pieces(max_len) * ACHIP_ZPACK_WIDE_REC_WORDS + ACHIP_ZPACK_FRM_WORDS);
+}
+
 /* frames i < n at base + i * stride, len_dev[i] bytes each (<= max_len): see asciichat_hip_frame_packets_zpacked.  Returns a
  * hipError_t. */
 int achip_launch_zpack(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
                        uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
                        uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
+/* the same over all 256 byte values (asciichat_hip_frame_packets_zpacked_wide); scratch: achip_zpack_wide_scratch_bytes */
+int achip_launch_zpack_wide(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
+                            uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
+                            uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -327,12 +327,23 @@ int asciichat_hip_frame_packets_packed(const uint8_t *base_dev, size_t stride, c
  * scratch_dev: device memory of asciichat_hip_zpack_scratch_bytes(max_len, n) bytes, 8-byte aligned, the call's own until
  * the work has run (calls in flight on different streams need different blocks).  Asynchronous, four launches on `stream`.
  * Only pieces whose bytes are all <= 0x80 are Huffman-coded (the tree travels in zstd's direct 4-bit form): half-block
- * frames and multi-byte palettes go out as they are.  No plan and no drop-in call chooses this form by itself. */
+ * frames and multi-byte palettes go out as they are -- the _wide entries below code those too.  No plan and no drop-in call
+ * chooses this form by itself. */
 size_t asciichat_hip_zpack_scratch_bytes(uint32_t max_len, int n);
 int asciichat_hip_frame_packets_zpacked(const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len, int n,
                                         const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
                                         uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                         uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream);
+/* ... and the WIDE form of the same pass: codes over all 256 byte values.  A piece whose largest byte is above 0x80 sends its
+ * Huffman tree in zstd's FSE-compressed weight form (Accuracy_Log 6), so half-block frames (E2 96 80) and
+ * multi-byte palettes are coded as well; a piece without such a byte comes out byte for byte as above.  Same parameters and
+ * contracts; scratch_dev holds asciichat_hip_zpack_wide_scratch_bytes(max_len, n) bytes (a larger record per piece).  Opt-in
+ * like the narrow form: no plan and no drop-in call chooses it by itself. */
+size_t asciichat_hip_zpack_wide_scratch_bytes(uint32_t max_len, int n);
+int asciichat_hip_frame_packets_zpacked_wide(const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len, int n,
+                                             const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
+                                             uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
+                                             uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream);
 
 /*
  * Compacted output (SURVEY.md 8e "prefer gathering compacted per-rank buffers ... lengths first").  A render leaves frame
@@ -495,6 +506,12 @@ int asciichat_hip_plan_render_packets_zpacked(asciichat_hip_plan_t *plan, uint8_
                                               uint8_t *hdr_out_dev, uint32_t *packet_crc_out_dev, uint8_t *dst,
                                               size_t dst_capacity, uint64_t *off_out, uint32_t *len_out, void *scratch_dev,
                                               size_t scratch_bytes, void *stream);
+/* ... with the wide form (asciichat_hip_frame_packets_zpacked_wide; scratch of asciichat_hip_zpack_wide_scratch_bytes) */
+int asciichat_hip_plan_render_packets_zpacked_wide(asciichat_hip_plan_t *plan, uint8_t *slab_dev, size_t out_stride,
+                                                   uint32_t *out_len_dev, const uint32_t *dims_dev, uint32_t *crc_out_dev,
+                                                   uint8_t *hdr_out_dev, uint32_t *packet_crc_out_dev, uint8_t *dst,
+                                                   size_t dst_capacity, uint64_t *off_out, uint32_t *len_out, void *scratch_dev,
+                                                   size_t scratch_bytes, void *stream);
 /* Exact-length frames beyond the 48 KB of the one-launch form above: LENGTH-FIRST -- the stream kernel's loop run twice,
  * lengths first, then the emission at the place the frame claimed (whole-frame plans of truecolor foreground with an all-ASCII
  * palette; ASCIICHAT_HIP_ERR_NOT_SUPPORTED otherwise).  Frames land in completion order (off_out[i], 16-byte aligned;
