@@ -673,6 +673,15 @@ class Plan:
         if rc != 0:
             raise RuntimeError(f"plan_render_packets_zpacked_wide failed ({rc}): {last_error()}")
 
+    def render_packets_zpacked_seq(self, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity,
+                                   off_ptr, len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+        """render + the sequence form of that stage (asciichat_hip_plan_render_packets_zpacked_seq; zpack_seq_scratch_bytes)"""
+        rc = _bind_zpack(lib()).asciichat_hip_plan_render_packets_zpacked_seq(self._h, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr,
+                                                                              hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                                                                              len_out_ptr, scratch_ptr, scratch_bytes, stream)
+        if rc != 0:
+            raise RuntimeError(f"plan_render_packets_zpacked_seq failed ({rc}): {last_error()}")
+
     def set_fused_crc(self, mode):
         """-1 automatic (fused where it is the faster form), 0 never, 1 wherever the geometry carries it"""
         rc = lib().asciichat_hip_plan_set_fused_crc(self._h, mode)
@@ -771,7 +780,7 @@ def _bind_zpack(L):
                             ("asciichat_hip_frame_packets_zpacked%s", ci, [vp, sz, vp, u32, ci, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
                             ("asciichat_hip_plan_render_packets_zpacked%s", ci, [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz,
                                                                                  vp])):
-        for form in ("", "_wide"):
+        for form in ("", "_wide", "_seq"):
             fn = getattr(L, name % form)
             fn.restype = res
             fn.argtypes = args
@@ -809,6 +818,22 @@ def frame_packets_zpacked_wide(base_ptr, stride, len_ptr, max_len, n, dims_ptr, 
                                                                      scratch_bytes, stream)
     if rc != 0:
         raise RuntimeError(f"frame_packets_zpacked_wide failed ({rc}): {last_error()}")
+
+
+def zpack_seq_scratch_bytes(max_len, n):
+    """bytes of device scratch a zpacked_seq call over n frames of up to max_len bytes needs"""
+    return int(_bind_zpack(lib()).asciichat_hip_zpack_seq_scratch_bytes(max_len, n))
+
+
+def frame_packets_zpacked_seq(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                              len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+    """asciichat_hip_frame_packets_zpacked_seq: frame_packets_zpacked_wide with the matches of a 64-byte window coded as zstd
+    sequences under the predefined tables, one block per 8192 bytes; scratch of zpack_seq_scratch_bytes"""
+    rc = _bind_zpack(lib()).asciichat_hip_frame_packets_zpacked_seq(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr,
+                                                                    pkt_ptr, dst_ptr, dst_capacity, off_ptr, len_out_ptr, scratch_ptr,
+                                                                    scratch_bytes, stream)
+    if rc != 0:
+        raise RuntimeError(f"frame_packets_zpacked_seq failed ({rc}): {last_error()}")
 
 
 class HostBuffer:

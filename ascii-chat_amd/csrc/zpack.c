@@ -4,7 +4,9 @@
  * frame (raw, RLE and Huffman-literals blocks, zero sequences: zpack_kernels.hpp) by the reference sender's own
  * rule.  Asynchronous: four launches on the caller's stream, the scratch is the caller's.  No plan and no drop-in entry takes
  * this form by itself.  The _wide entries are the same pass over all 256 byte values (the tree in zstd's FSE-compressed form
- * where a piece holds a byte above 0x80), with a larger scratch record; they are as opt-in as the narrow ones.
+ * where a piece holds a byte above 0x80), with a larger scratch record; they are as opt-in as the narrow ones.  The _seq entries
+ * are the sequence form (zseq_kernels.hpp): blocks of 8 KB, matches of a 64-byte window as zstd sequences under the predefined
+ * tables, the other bytes as the wide form's literals; opt-in likewise, with a scratch of its own layout.
  */
 #include <stdint.h>
 
@@ -24,8 +26,16 @@ size_t asciichat_hip_zpack_wide_scratch_bytes(uint32_t max_len, int n) {
   return achip_zpack_wide_scratch_bytes(max_len, n);
 }
 
-/* either form: `what` names the entry in messages */
-static int frame_packets_zpacked(int wide, const char *what, const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len,
+size_t asciichat_hip_zpack_seq_scratch_bytes(uint32_t max_len, int n) {
+  if (max_len == 0 || max_len >= 0xFFFFFFF0u)
+    return 0;
+  return achip_zseq_scratch_bytes(max_len, n);
+}
+
+enum { FORM_NARROW = 0, FORM_WIDE = 1, FORM_SEQ = 2 };
+
+/* any form: `what` names the entry in messages */
+static int frame_packets_zpacked(int form, const char *what, const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len,
                                  int n, const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev, uint32_t *packet_crc_out_dev,
                                  uint8_t *dst, size_t dst_capacity, uint64_t *off_out, uint32_t *len_out, void *scratch_dev,
                                  size_t scratch_bytes, void *stream) {
@@ -35,26 +45,30 @@ static int frame_packets_zpacked(int wide, const char *what, const uint8_t *base
   if (!len_dev || !hdr_out_dev || !dst || ((uintptr_t)dst & 15u) || ((uintptr_t)off_out & 7u) || ((uintptr_t)len_out & 3u) ||
       ((uintptr_t)hdr_out_dev & 7u))
     return achip_fail(ASCIICHAT_HIP_ERR_INVALID_PARAM, "%s: lengths, a header buffer and a 16-byte aligned destination are required", what);
-  if ((uint64_t)n * achip_zpack_pieces(max_len) > 0x7FFFFFFFull)
+  if ((uint64_t)n * (form == FORM_SEQ ? achip_zseq_pieces(max_len) : achip_zpack_pieces(max_len)) > 0x7FFFFFFFull)
     return achip_fail(ASCIICHAT_HIP_ERR_INVALID_PARAM, "%s: %d frames of up to %u bytes are more pieces than a launch takes", what, n, max_len);
-  const size_t need = wide ? achip_zpack_wide_scratch_bytes(max_len, n) : achip_zpack_scratch_bytes(max_len, n);
+  const size_t need = form == FORM_SEQ    ? achip_zseq_scratch_bytes(max_len, n)
+                      : form == FORM_WIDE ? achip_zpack_wide_scratch_bytes(max_len, n)
+                                          : achip_zpack_scratch_bytes(max_len, n);
   if (!scratch_dev || ((uintptr_t)scratch_dev & 7u) || scratch_bytes < need)
     return achip_fail(ASCIICHAT_HIP_ERR_INVALID_PARAM, "%s: an 8-byte aligned scratch of %zu bytes is required (%zu given)", what, need,
                       scratch_bytes);
   const int rc = achip_require_device();
   if (rc)
     return rc;
-  return achip_hip_check((wide ? achip_launch_zpack_wide : achip_launch_zpack)(base_dev, (uint64_t)stride, len_dev, max_len, n, dims_dev, crc_out_dev,
-                                                                               hdr_out_dev, packet_crc_out_dev, dst, (uint64_t)dst_capacity,
-                                                                               off_out, len_out, (uint32_t *)scratch_dev, stream),
-                         wide ? "zpack wide launch" : "zpack launch");
+  return achip_hip_check((form == FORM_SEQ    ? achip_launch_zseq
+                          : form == FORM_WIDE ? achip_launch_zpack_wide
+                                              : achip_launch_zpack)(base_dev, (uint64_t)stride, len_dev, max_len, n, dims_dev, crc_out_dev, hdr_out_dev,
+                                                                    packet_crc_out_dev, dst, (uint64_t)dst_capacity, off_out, len_out,
+                                                                    (uint32_t *)scratch_dev, stream),
+                         form == FORM_SEQ ? "zseq launch" : form == FORM_WIDE ? "zpack wide launch" : "zpack launch");
 }
 
 int asciichat_hip_frame_packets_zpacked(const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len, int n,
                                         const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
                                         uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                         uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream) {
-  return frame_packets_zpacked(0, "frame_packets_zpacked", base_dev, stride, len_dev, max_len, n, dims_dev, crc_out_dev, hdr_out_dev,
+  return frame_packets_zpacked(FORM_NARROW, "frame_packets_zpacked", base_dev, stride, len_dev, max_len, n, dims_dev, crc_out_dev, hdr_out_dev,
                                packet_crc_out_dev, dst, dst_capacity, off_out, len_out, scratch_dev, scratch_bytes, stream);
 }
 
@@ -62,13 +76,21 @@ int asciichat_hip_frame_packets_zpacked_wide(const uint8_t *base_dev, size_t str
                                              const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
                                              uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                              uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream) {
-  return frame_packets_zpacked(1, "frame_packets_zpacked_wide", base_dev, stride, len_dev, max_len, n, dims_dev, crc_out_dev, hdr_out_dev,
+  return frame_packets_zpacked(FORM_WIDE, "frame_packets_zpacked_wide", base_dev, stride, len_dev, max_len, n, dims_dev, crc_out_dev, hdr_out_dev,
+                               packet_crc_out_dev, dst, dst_capacity, off_out, len_out, scratch_dev, scratch_bytes, stream);
+}
+
+int asciichat_hip_frame_packets_zpacked_seq(const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len, int n,
+                                            const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
+                                            uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
+                                            uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream) {
+  return frame_packets_zpacked(FORM_SEQ, "frame_packets_zpacked_seq", base_dev, stride, len_dev, max_len, n, dims_dev, crc_out_dev, hdr_out_dev,
                                packet_crc_out_dev, dst, dst_capacity, off_out, len_out, scratch_dev, scratch_bytes, stream);
 }
 
 /* plan render + the pass above on one stream.  Always these two steps: the plan's own choices among the packed forms do not
  * apply here, and no plan takes this form by itself. */
-static int plan_render_packets_zpacked(int wide, const char *what, asciichat_hip_plan_t *p, uint8_t *slab_dev, size_t out_stride,
+static int plan_render_packets_zpacked(int form, const char *what, asciichat_hip_plan_t *p, uint8_t *slab_dev, size_t out_stride,
                                        uint32_t *out_len_dev, const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
                                        uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out, uint32_t *len_out,
                                        void *scratch_dev, size_t scratch_bytes, void *stream) {
@@ -78,7 +100,8 @@ static int plan_render_packets_zpacked(int wide, const char *what, asciichat_hip
     return achip_fail(ASCIICHAT_HIP_ERR_INVALID_PARAM, "plan_render_packets_%s: stride %zu", what, out_stride);
   int rc = asciichat_hip_plan_render(p, slab_dev, out_stride, out_len_dev, stream);
   if (!rc)
-    rc = frame_packets_zpacked(wide, wide ? "frame_packets_zpacked_wide" : "frame_packets_zpacked", slab_dev, out_stride, out_len_dev,
+    rc = frame_packets_zpacked(form, form == FORM_SEQ ? "frame_packets_zpacked_seq" : form == FORM_WIDE ? "frame_packets_zpacked_wide" : "frame_packets_zpacked",
+                               slab_dev, out_stride, out_len_dev,
                                (uint32_t)out_stride, achip_plan_frame_count(p), dims_dev, crc_out_dev, hdr_out_dev, packet_crc_out_dev, dst,
                                dst_capacity, off_out, len_out, scratch_dev, scratch_bytes, stream);
   return rc;
@@ -88,7 +111,7 @@ int asciichat_hip_plan_render_packets_zpacked(asciichat_hip_plan_t *p, uint8_t *
                                               const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
                                               uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                               uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream) {
-  return plan_render_packets_zpacked(0, "zpacked", p, slab_dev, out_stride, out_len_dev, dims_dev, crc_out_dev, hdr_out_dev, packet_crc_out_dev,
+  return plan_render_packets_zpacked(FORM_NARROW, "zpacked", p, slab_dev, out_stride, out_len_dev, dims_dev, crc_out_dev, hdr_out_dev, packet_crc_out_dev,
                                      dst, dst_capacity, off_out, len_out, scratch_dev, scratch_bytes, stream);
 }
 
@@ -96,6 +119,14 @@ int asciichat_hip_plan_render_packets_zpacked_wide(asciichat_hip_plan_t *p, uint
                                                    const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
                                                    uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                                    uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream) {
-  return plan_render_packets_zpacked(1, "zpacked_wide", p, slab_dev, out_stride, out_len_dev, dims_dev, crc_out_dev, hdr_out_dev,
+  return plan_render_packets_zpacked(FORM_WIDE, "zpacked_wide", p, slab_dev, out_stride, out_len_dev, dims_dev, crc_out_dev, hdr_out_dev,
+                                     packet_crc_out_dev, dst, dst_capacity, off_out, len_out, scratch_dev, scratch_bytes, stream);
+}
+
+int asciichat_hip_plan_render_packets_zpacked_seq(asciichat_hip_plan_t *p, uint8_t *slab_dev, size_t out_stride, uint32_t *out_len_dev,
+                                                  const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
+                                                  uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
+                                                  uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream) {
+  return plan_render_packets_zpacked(FORM_SEQ, "zpacked_seq", p, slab_dev, out_stride, out_len_dev, dims_dev, crc_out_dev, hdr_out_dev,
                                      packet_crc_out_dev, dst, dst_capacity, off_out, len_out, scratch_dev, scratch_bytes, stream);
 }

@@ -75,6 +75,33 @@ static inline size_t achip_zpack_wide_scratch_bytes(uint32_t max_len, int n) {
   return 4u * (size_t)n * ((size_t)achip_zpack_pieces(max_len) * ACHIP_ZPACK_WIDE_REC_WORDS + ACHIP_ZPACK_FRM_WORDS);
 }
 
+/* ---- the sequence form ("zseq", zseq_kernels.hpp): the frame cut every ACHIP_ZSEQ_PIECE bytes, a block's matches in a 64-byte
+ * window as a sequences section under the predefined tables, its other bytes as the wide form's literals section.  A piece's
+ * record is the words ZR_KIND .. ZR_BLEN above (ZR_STREAM .. ZR_FMT unused); behind the records of the frames lies one slot per
+ * (frame, piece) that holds a compressed block's body between the pass that builds it and the pass that places it. */
+#ifndef ACHIP_ZSEQ_PIECE /* (only the second emulator library of the tests defines it, smaller) */
+#define ACHIP_ZSEQ_PIECE 8192u
+#endif
+#ifdef __cplusplus
+static_assert(ACHIP_ZSEQ_PIECE % 16u == 0u && ACHIP_ZSEQ_PIECE >= 64u && ACHIP_ZSEQ_PIECE <= 8192u, "a piece and its arrays live in LDS (zseq_kernels.hpp: BLds); the window of the next one lies inside it");
+#else
+_Static_assert(ACHIP_ZSEQ_PIECE % 16u == 0u && ACHIP_ZSEQ_PIECE >= 64u && ACHIP_ZSEQ_PIECE <= 8192u, "a piece and its arrays live in LDS (zseq_kernels.hpp: BLds); the window of the next one lies inside it");
+#endif
+#define ACHIP_ZSEQ_REC_WORDS 16
+static inline uint32_t achip_zseq_pieces(uint32_t max_len) {
+  return max_len <= ACHIP_ZSEQ_PIECE ? 1u : (uint32_t)(((uint64_t)max_len + ACHIP_ZSEQ_PIECE - 1u) / ACHIP_ZSEQ_PIECE);
+}
+/* bytes of a body slot: a compressed block is shorter than its piece */
+static inline uint32_t achip_zseq_slot_bytes(uint32_t max_len) {
+  return ((max_len < ACHIP_ZSEQ_PIECE ? max_len : ACHIP_ZSEQ_PIECE) + 15u) & ~15u;
+}
+/* records of the pieces, records of the frames, body slots */
+static inline size_t achip_zseq_scratch_bytes(uint32_t max_len, int n) {
+  if (n <= 0)
+    return 0;
+  return (size_t)n * ((size_t)achip_zseq_pieces(max_len) * (4u * ACHIP_ZSEQ_REC_WORDS + achip_zseq_slot_bytes(max_len)) + 4u * ACHIP_ZPACK_FRM_WORDS);
+}
+
 /* frames i < n at base + i * stride, len_dev[i] bytes each (<= max_len): see asciichat_hip_frame_packets_zpacked.  Returns a
  * hipError_t. */
 int achip_launch_zpack(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
@@ -84,6 +111,11 @@ int achip_launch_zpack(const uint8_t *base, uint64_t stride, const uint32_t *len
 int achip_launch_zpack_wide(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
                             uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
                             uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
+
+/* the sequence form (asciichat_hip_frame_packets_zpacked_seq); scratch: achip_zseq_scratch_bytes */
+int achip_launch_zseq(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
+                      uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
+                      uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -465,8 +465,8 @@ __global__ void __launch_bounds__(ACHIP_ZPACK_BLOCK)
   }
 }
 
-/* ONE workgroup: the frame rule, the layout, the frame checksums */
-template <int RecWords = ACHIP_ZPACK_REC_WORDS>
+/* ONE workgroup: the frame rule, the layout, the frame checksums.  Piece: bytes of a frame per block (the sequence form cuts finer). */
+template <int RecWords = ACHIP_ZPACK_REC_WORDS, uint32_t Piece = ACHIP_ZPACK_PIECE>
 __global__ void __launch_bounds__(ACHIP_ZPACK_BLOCK)
     zpack_plan_kernel(const uint32_t *__restrict__ len, int n_frames, uint32_t pieces, uint32_t *__restrict__ scratch, uint64_t capacity,
                       uint64_t *__restrict__ off_out, uint32_t *__restrict__ len_out, uint32_t *__restrict__ crc_out) {
@@ -480,7 +480,7 @@ __global__ void __launch_bounds__(ACHIP_ZPACK_BLOCK)
     const uint32_t raw_len = len[i];
     const bool bad = raw_len >= 0xFFFFFFF0u;
     const uint32_t L = bad ? 0u : raw_len;
-    const uint32_t np = bad ? 0u : max(1u, (uint32_t)(((uint64_t)L + kPiece - 1u) / kPiece));
+    const uint32_t np = bad ? 0u : max(1u, (uint32_t)(((uint64_t)L + Piece - 1u) / Piece));
     uint64_t zlen = 9u;
     uint32_t st = 0xFFFFFFFFu;
     for (uint32_t p = 0; p < np; p++) {

@@ -345,6 +345,21 @@ int asciichat_hip_frame_packets_zpacked_wide(const uint8_t *base_dev, size_t str
                                              uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
                                              uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream);
 
+/* ... and the SEQUENCE form: the frame is cut into zstd blocks of 8192 bytes; in every block the bytes that repeat within the 64
+ * bytes in front of them (the ESC[38;2; / ESC[48;2; prefix of every cell) travel as match sequences under zstd's predefined
+ * tables, the other bytes as the wide form's literals section ("sequence form"); every libzstd decodes the frame.
+ * Same parameters and contracts as the two forms above -- hdr / crc / packet_crc / dst / off_out / len_out, the checksum over the
+ * ORIGINAL bytes, the sender's 0.8 rule, nothing stored at or behind dst + dst_capacity, error codes and empty frames take no
+ * room, asynchronous on `stream`; scratch_dev holds asciichat_hip_zpack_seq_scratch_bytes(max_len, n) bytes, 8-byte aligned:
+ * 64 bytes per block and 32 per frame of records, and per block a slot of min(8192, max_len) bytes (rounded to 16) that holds a
+ * compressed block between the launch that builds it and the one that places it.  Opt-in like the other two: no plan and no
+ * drop-in call chooses it by itself. */
+size_t asciichat_hip_zpack_seq_scratch_bytes(uint32_t max_len, int n);
+int asciichat_hip_frame_packets_zpacked_seq(const uint8_t *base_dev, size_t stride, const uint32_t *len_dev, uint32_t max_len, int n,
+                                            const uint32_t *dims_dev, uint32_t *crc_out_dev, uint8_t *hdr_out_dev,
+                                            uint32_t *packet_crc_out_dev, uint8_t *dst, size_t dst_capacity, uint64_t *off_out,
+                                            uint32_t *len_out, void *scratch_dev, size_t scratch_bytes, void *stream);
+
 /*
  * Compacted output (SURVEY.md 8e "prefer gathering compacted per-rank buffers ... lengths first").  A render leaves frame
  * i at slab + i*stride, stride = the worst case (44.5 KB for 80x24 truecolor; real video is 2-4 KB per frame).  What
@@ -512,6 +527,12 @@ int asciichat_hip_plan_render_packets_zpacked_wide(asciichat_hip_plan_t *plan, u
                                                    uint8_t *hdr_out_dev, uint32_t *packet_crc_out_dev, uint8_t *dst,
                                                    size_t dst_capacity, uint64_t *off_out, uint32_t *len_out, void *scratch_dev,
                                                    size_t scratch_bytes, void *stream);
+/* ... with the sequence form (asciichat_hip_frame_packets_zpacked_seq; scratch of asciichat_hip_zpack_seq_scratch_bytes) */
+int asciichat_hip_plan_render_packets_zpacked_seq(asciichat_hip_plan_t *plan, uint8_t *slab_dev, size_t out_stride,
+                                                  uint32_t *out_len_dev, const uint32_t *dims_dev, uint32_t *crc_out_dev,
+                                                  uint8_t *hdr_out_dev, uint32_t *packet_crc_out_dev, uint8_t *dst,
+                                                  size_t dst_capacity, uint64_t *off_out, uint32_t *len_out, void *scratch_dev,
+                                                  size_t scratch_bytes, void *stream);
 /* Exact-length frames beyond the 48 KB of the one-launch form above: LENGTH-FIRST -- the stream kernel's loop run twice,
  * lengths first, then the emission at the place the frame claimed (whole-frame plans of truecolor foreground with an all-ASCII
  * palette; ASCIICHAT_HIP_ERR_NOT_SUPPORTED otherwise).  Frames land in completion order (off_out[i], 16-byte aligned;
