@@ -1072,6 +1072,11 @@ int asciichat_hip_composite_upload(const achip_composite_t *comp_host, achip_com
   achip_composite_t *d = NULL;
   achip_composite_t copy = *comp_host;
   copy._pad = 0; /* the kernels read this word as the pixel of a sample that hits no tile (sample_composite_lds) */
+  /* a grid without cells (no columns or rows, or a cell size that is not positive: more grid rows than canvas rows) is black
+   * everywhere for the global sampler (sample_composite); the staged one divides by such a size as by 1 and would still light
+   * the tiles of a descriptor filled by hand -- without placed sources both render black */
+  if (copy.cols <= 0 || copy.rows <= 0 || copy.cell_w <= 0 || copy.cell_h <= 0)
+    copy.n_src = 0;
   rc = achip_hip_check((int)hipMalloc((void **)&d, sizeof(*d)), "hipMalloc(composite)");
   if (!rc)
     rc = achip_hip_check((int)hipMemcpy(d, &copy, sizeof(*d), hipMemcpyHostToDevice), "hipMemcpy(composite)");

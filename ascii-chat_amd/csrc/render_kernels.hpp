@@ -511,6 +511,10 @@ __device__ inline uint32_t tint_pixel(uint32_t p, uint32_t ops) {
  * contains it, nearest-neighbour resized on the fly; black outside every tile. */
 __device__ inline uint32_t sample_composite(const achip_composite_t *__restrict__ cgen, uint32_t X, uint32_t Y) {
   const ACHIP_GLOBAL achip_composite_t *c = (const ACHIP_GLOBAL achip_composite_t *)cgen;
+  /* no grid, or more grid rows than canvas rows (nine sources on a canvas 8 pixels high: cell_h == 0): all black, as the
+   * staged sampler below renders it -- a division by zero traps on a CPU and returns any quotient on the device */
+  if (c->cell_w <= 0 || c->cell_h <= 0)
+    return 0u;
   const int col = (int)X / c->cell_w, row = (int)Y / c->cell_h;
   if (col >= c->cols || row >= c->rows)
     return 0u;
