@@ -463,6 +463,7 @@ def _bind_box(L):
                             ("asciichat_hip_box_run", ci, [vp, vp, sz, vp]),
                             ("asciichat_hip_box_get_uniform", ci, [vp]),
                             ("asciichat_hip_box_render_frames", ci, [vp, vp, sz, C.POINTER(Frame)]),
+                            ("asciichat_hip_box_composites", ci, [C.POINTER(vp), C.POINTER(Frame), C.POINTER(vp), ci, vp]),
                             ("asciichat_hip_box_destroy", None, [vp]),
                             ("asciichat_hip_box_downscale", ci, [vp, ci, ci, ci, vp, ci, ci, ci, ci, vp])):
         fn = getattr(L, name)
@@ -478,24 +479,41 @@ class Box:
     averaged image is what matches the reference's renderer over that image.  Use: Box(frames), render_frames(images),
     Plan(mode, palette, those); per tick update(), run(), plan.render() on one stream."""
 
-    def __init__(self, frames):
+    def __init__(self, frames, comps=None, stream=0):
+        """comps (asciichat_hip_box_composites): per frame None (a plain frame) or the HOST Composite that frame is averaged
+        from -- tiles, canvas, averaged canvas, rounded twice; its sources device-visible.  Without comps: box_create."""
         self.L = _bind_box(lib())
         self.n = len(frames)
         self._arr = (Frame * self.n)(*frames)
         self._h = C.c_void_p()
-        rc = self.L.asciichat_hip_box_create(C.byref(self._h), self._arr, self.n)
+        if comps is None:
+            rc = self.L.asciichat_hip_box_create(C.byref(self._h), self._arr, self.n)
+        else:
+            rc = self.L.asciichat_hip_box_composites(C.byref(self._h), self._arr, self._comp_array(comps), self.n, stream)
         if rc != 0:
-            raise RuntimeError(f"asciichat_hip_box_create failed ({rc}): {last_error()}")
+            raise RuntimeError(f"asciichat_hip_box_{'create' if comps is None else 'composites'} failed ({rc}): {last_error()}")
         self.pitch = int(self.L.asciichat_hip_box_image_pitch(self._h))
+
+    def _comp_array(self, comps):
+        if len(comps) != self.n:
+            raise ValueError(f"{len(comps)} composites for {self.n} frames")
+        self._comps = list(comps)  # (the library copies what it needs; kept for the duration of the call)
+        return (C.c_void_p * self.n)(*[C.addressof(c) if c is not None else None for c in comps])
 
     @property
     def uniform(self):
         """True when launches pass the batch's common descriptor in the kernel arguments"""
         return bool(self.L.asciichat_hip_box_get_uniform(self._h))
 
-    def update(self, frames, stream=0):
+    def update(self, frames, stream=0, comps=None):
+        """the next tick's descriptors, in stream order with run(); comps as in Box(): without them every frame is plain"""
         self._arr = frames if isinstance(frames, C.Array) else (Frame * self.n)(*frames)
-        rc = self.L.asciichat_hip_box_update(self._h, self._arr, stream)
+        if comps is None:
+            rc = self.L.asciichat_hip_box_update(self._h, self._arr, stream)
+        else:
+            if len(self._arr) != self.n:
+                raise ValueError(f"{len(self._arr)} frames for a box of {self.n}")
+            rc = self.L.asciichat_hip_box_composites(C.byref(self._h), self._arr, self._comp_array(comps), self.n, stream)
         if rc != 0:
             raise RuntimeError(f"box_update failed ({rc}): {last_error()}")
         self.pitch = int(self.L.asciichat_hip_box_image_pitch(self._h))

@@ -22,6 +22,16 @@
  * Row offsets are 64-bit (2159 rows of 11520 bytes pass 2^24: no 24-bit multiply anywhere), sums are 32-bit (an all-255
  * 3840 x 2160 frame averaged to 1 x 1 sums to 2 115 072 000; with n / 2 added still below 2^32).
  * Only plain HIP: the same source runs under the CPU emulator (tests/hipemu).
+ *
+ * Grid composites (box_canvas_kernel): a composite frame is averaged in two exact steps, each rounded -- every placed source
+ * k to its tile T_k (tile_w x tile_h, no flips) by box_kernel into a scratch slab, then the canvas_w x canvas_h canvas, whose
+ * pixel (X, Y) is T_k[Y - org_y][X - org_x] under the cell lookup of sample_composite (render_kernels.hpp) and black
+ * elsewhere, to out_w x out_h by the same rule (black pixels count in n; flips mirror the result).  The canvas is never
+ * stored: one 256-thread workgroup per (composite frame, stored output row) sums the canvas rows of the row's box per byte
+ * column straight from the tiles.  A lane owns byte columns j = lane, lane + 256, ... < 3 * canvas_w, resolves the column's
+ * cell column once, and walks the rows [y0, y1) one cell row at a time (the cell changes only at multiples of cell_h):
+ * within a cell the column's bytes are 3 * tile_w apart in one tile.  Sums go to the same LDS stage (12 * canvas_w bytes,
+ * one owner per column, nothing atomic); phase 2 is box_kernel's.  No division by a cell size of 0: such a canvas is black.
  */
 #pragma once
 
@@ -146,6 +156,62 @@ __global__ void __launch_bounds__(ACHIP_BOX_BLOCK)
     uint32_t s = 0u;
     for (uint32_t k = x0; k < x1; k++)
       s += sums[3u * k + c];
+    const uint32_t n = (x1 - x0) * (y1 - y0);
+    out[j] = (uint8_t)((s + n / 2u) / n);
+  }
+}
+
+/* workgroup b: composite frame b / rows_per_frame of the table, stored row b % rows_per_frame */
+__global__ void __launch_bounds__(ACHIP_BOX_BLOCK)
+    box_canvas_kernel(const achip_box_canvas_t *__restrict__ table, const uint32_t rows_per_frame, const uint8_t *__restrict__ tiles,
+                      const uint64_t tile_pitch, uint8_t *__restrict__ images, const uint64_t pitch) {
+  const uint32_t k = blockIdx.x / rows_per_frame, y = blockIdx.x - k * rows_per_frame;
+  const achip_box_canvas_t *__restrict__ t = table + k;
+  const uint32_t canvas_w = (uint32_t)t->canvas_w, canvas_h = (uint32_t)t->canvas_h, out_w = (uint32_t)t->out_w,
+                 out_h = (uint32_t)t->out_h, flips = t->flips;
+  if (y >= out_h)
+    return;
+  uint32_t y0, y1;
+  bounds(canvas_h, out_h, (flips & ACHIP_OP_FLIP_Y) ? out_h - 1u - y : y, y0, y1);
+  uint32_t *sums = reinterpret_cast<uint32_t *>(ACHIP_SMEM);
+  const bool grid = t->cell_w > 0 && t->cell_h > 0;
+  const uint32_t cell_w = (uint32_t)t->cell_w, cell_h = (uint32_t)t->cell_h, cols = (uint32_t)t->cols, rows = (uint32_t)t->rows,
+                 n_src = (uint32_t)t->n_src;
+  for (uint32_t j = threadIdx.x; j < 3u * canvas_w; j += kBlock) {
+    const uint32_t X = j / 3u;
+    uint32_t s = 0u;
+    const uint32_t col = grid ? X / cell_w : cols; /* (never a division by 0) */
+    if (col < cols) {
+      uint32_t row = y0 / cell_h;
+      for (uint32_t Y = y0; Y < y1 && row < rows; row++) {
+        const uint32_t Yend = min(y1, (row + 1u) * cell_h); /* the rows of [Y, y1) in this cell row */
+        const uint64_t idx = (uint64_t)row * cols + col;
+        if (idx >= n_src)
+          break; /* so is every later cell row */
+        const achip_box_cell_t *__restrict__ cell = &t->cell[idx];
+        const int32_t slot = cell->slot, lx = (int32_t)X - cell->org_x;
+        if (slot >= 0 && lx >= 0 && lx < cell->tile_w) {
+          const int32_t ya = max((int32_t)Y, cell->org_y), yb = min((int32_t)Yend, cell->org_y + cell->tile_h);
+          const uint32_t step = 3u * (uint32_t)cell->tile_w;
+          const ACHIP_GLOBAL uint8_t *p = (const ACHIP_GLOBAL uint8_t *)tiles + (uint64_t)slot * tile_pitch +
+                                          (uint64_t)(uint32_t)(ya - cell->org_y) * step + (j - 3u * (uint32_t)cell->org_x);
+          for (int32_t yy = ya; yy < yb; yy++, p += step)
+            s += *p;
+        }
+        Y = Yend;
+      }
+    }
+    sums[j] = s;
+  }
+  __syncthreads();
+  uint8_t *out = images + (uint64_t)(uint32_t)t->frame * pitch + (uint64_t)y * (3u * out_w);
+  for (uint32_t j = threadIdx.x; j < 3u * out_w; j += kBlock) {
+    const uint32_t x = j / 3u, c = j - 3u * x;
+    uint32_t x0, x1;
+    bounds(canvas_w, out_w, (flips & ACHIP_OP_FLIP_X) ? out_w - 1u - x : x, x0, x1);
+    uint32_t s = 0u;
+    for (uint32_t i = x0; i < x1; i++)
+      s += sums[3u * i + c];
     const uint32_t n = (x1 - x0) * (y1 - y0);
     out[j] = (uint8_t)((s + n / 2u) / n);
   }

@@ -175,8 +175,10 @@ int asciichat_hip_resize(const uint8_t *src_dev, int src_w, int src_h, uint8_t *
  * A[y][x] = (S + n / 2) / n with S the sum over the box and n its pixels.  The ACHIP_OP_FLIP_X / _Y bits of `ops` mirror the
  * averaged image: stored pixel (x, y) = A[fy ? out_h - 1 - y : y][fx ? out_w - 1 - x : x].  Tints, the foreground override,
  * dither bits and padding stay in the descriptor for the render.  Sources of 1..3840 x 1..2160 at any alignment and any
- * src_stride >= 3 * src_w (0 = tight), averaged sizes up to 16384 a side.  comp != NULL: ASCIICHAT_HIP_ERR_NOT_SUPPORTED; a
- * NULL source, non-positive or oversize dimensions, a short stride: ASCIICHAT_HIP_ERR_INVALID_PARAM.
+ * src_stride >= 3 * src_w (0 = tight), averaged sizes up to 16384 a side.  A plain frame (box_create, box_update,
+ * box_downscale, and box_composites where comps_host[i] == NULL) with comp != NULL: ASCIICHAT_HIP_ERR_NOT_SUPPORTED -- comp is
+ * a device pointer; composites are averaged from their host descriptors by box_composites, below; a NULL source,
+ * non-positive or oversize dimensions, a short stride: ASCIICHAT_HIP_ERR_INVALID_PARAM.
  *
  * box_create(frames) takes the tick's render descriptors as achip_frame_setup() made them (host array; src device-visible);
  * box_update the next tick's (same n; in stream order with box_run; a refused or failed update leaves the box as it was).
@@ -188,6 +190,29 @@ int asciichat_hip_resize(const uint8_t *src_dev, int src_w, int src_h, uint8_t *
  * plan_create(mode, palette, frames_out); per tick box_update, box_run, plan_render on one stream.
  * box_get_uniform: 1 when the batch's common descriptor travels in the kernel arguments (equal geometry, constant pitch).
  * box_downscale: one image, beside asciichat_hip_resize (dst_dev holds 3 * dst_w * dst_h bytes).
+ *
+ * box_composites: the pixel-space grid composite (achip_composite_setup) through the pass.  *box == NULL creates a box (like
+ * box_create its descriptors are on the device on return; the first box_run may go to any stream), else it updates *box in
+ * stream order with box_run (n_frames must be the box's; a refused or failed call leaves the box as it was).
+ * comps_host[i] == NULL: frame i is a plain frame under the rules above.  Otherwise frame i is averaged from the HOST
+ * descriptor comps_host[i] (source pointers in it device-visible); frames[i].src and frames[i].comp are not read, and
+ * frames[i].src_w x src_h must be the canvas.  Still integer and exact, and rounded TWICE: (1) every placed source k (k < n_src,
+ * src != NULL) is averaged to its tile T_k, tile_w x tile_h, by the rule above without flips (x_ratio / y_ratio are not read);
+ * (2) canvas pixel (X, Y) is T_k[Y - org_y][X - org_x] where the renderers' composite lookup finds tile k -- cell_w, cell_h > 0,
+ * X / cell_w < cols, Y / cell_h < rows, k = (Y / cell_h) * cols + X / cell_w < n_src, src != NULL, 0 <= X - org_x < tile_w,
+ * 0 <= Y - org_y < tile_h: a tile is clipped by its cell -- and black elsewhere; (3) the canvas is averaged to out_w x out_h by
+ * the same rule, black pixels counting in n, and the flips mirror the result.  The result is by definition the composition
+ * of two runs of the plain pass.  cell_w <= 0, cell_h <= 0 or n_src == 0: a black image.  ASCIICHAT_HIP_ERR_INVALID_PARAM, the
+ * message naming the frame: a canvas outside 1..3840 x 1..2160 or different from the frame's src_w x src_h, out_w / out_h
+ * outside 1..16384, n_src outside 0..9, negative cols or rows; for a placed source a size outside a plain frame's limits,
+ * src_stride < 3 * src_w, tile_w / tile_h outside 1..canvas size.  Tiles are shared over the batch: targets of one terminal
+ * size read their sources once.  box_update treats every frame as plain; box_run, box_image_pitch and box_render_frames serve
+ * either kind of box; box_render_frames rewrites a composite frame like a plain one (comp NULL), so a tint bit in ops
+ * APPLIES to the averaged image where the point-sampled composite samplers ignore tints; box_get_uniform is 0 for a batch
+ * that holds a composite frame.  An update (either entry) waits on the GPU in two cases only: four earlier updates all still
+ * in flight, and a batch that needs more tile scratch than the box holds (a larger slab is allocated and `stream`
+ * synchronised before the old one is freed).  Opt-in and non-parity like the rest of the pass; the drop-in layer has no
+ * switch for it.
  */
 typedef struct asciichat_hip_box asciichat_hip_box_t;
 int asciichat_hip_box_create(asciichat_hip_box_t **box, const achip_frame_t *frames, int n_frames);
@@ -197,6 +222,8 @@ int asciichat_hip_box_run(asciichat_hip_box_t *box, uint8_t *images_dev, size_t 
 int asciichat_hip_box_get_uniform(const asciichat_hip_box_t *box);
 int asciichat_hip_box_render_frames(const asciichat_hip_box_t *box, const uint8_t *images_dev, size_t pitch,
                                     achip_frame_t *frames_out);
+int asciichat_hip_box_composites(asciichat_hip_box_t **box, const achip_frame_t *frames, const achip_composite_t *const *comps_host,
+                                 int n_frames, void *stream);
 void asciichat_hip_box_destroy(asciichat_hip_box_t *box);
 int asciichat_hip_box_downscale(const uint8_t *src_dev, int src_w, int src_h, int src_stride, uint8_t *dst_dev, int dst_w,
                                 int dst_h, int flip_x, int flip_y, void *stream);
