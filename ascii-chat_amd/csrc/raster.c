@@ -1,0 +1,197 @@
+/*
+ * raster.c -- the host side of libasciichat_raster.so (include/asciichat_raster.h): a handle checks its font and grid before
+ * it needs a device (raster.h), uploads the atlas and the lookup tables once and owns every byte of scratch a run uses --
+ * cells, row starts and row records for max_frames frames --, so that run() only launches (raster.hip) on the caller's
+ * stream.  Nothing here comes from libasciichat_hip.so.
+ */
+#define __HIP_PLATFORM_AMD__ 1
+#include <hip/hip_runtime_api.h>
+
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "asciichat_raster.h"
+#include "raster.h"
+
+#define RASTER_MAGIC 0x5241535445523031ull
+
+struct asciichat_raster {
+  uint64_t magic;
+  int device, max_frames;
+  raster_params_t p;
+  uint8_t *tables; /* one allocation: codepoints, glyphs, lut, coverage */
+  uint32_t *starts;
+  raster_rowrec_t *recs;
+  raster_cell_t *cells;
+};
+
+static _Thread_local char g_error[256];
+
+static int fail(int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_error, sizeof(g_error), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+static int hip_check(hipError_t e, const char *what) {
+  if (e == hipSuccess)
+    return 0;
+  return fail(e == hipErrorOutOfMemory ? ASCIICHAT_RASTER_ERR_MEMORY : ASCIICHAT_RASTER_ERR_NO_DEVICE, "%s: %s", what, hipGetErrorString(e));
+}
+
+const char *asciichat_raster_last_error(void) { return g_error; }
+
+int asciichat_raster_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess)
+    return 0;
+  return n;
+}
+
+static asciichat_raster_t *raster_of(const asciichat_raster_t *r) { return r && r->magic == RASTER_MAGIC ? (asciichat_raster_t *)r : NULL; }
+
+static void raster_free(asciichat_raster_t *h) {
+  (void)hipFree(h->cells);
+  (void)hipFree(h->recs);
+  (void)hipFree(h->starts);
+  (void)hipFree(h->tables);
+  h->magic = 0;
+  free(h);
+}
+
+static size_t round16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+
+int asciichat_raster_create(asciichat_raster_t **r, const asciichat_raster_font_t *font, int cols, int rows, int max_frames) {
+  if (!r)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_create: no handle");
+  *r = NULL;
+  const char *why = raster_check(font, cols, rows, max_frames);
+  if (why)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_create: %s", why);
+  if (asciichat_raster_device_count() <= 0)
+    return fail(ASCIICHAT_RASTER_ERR_NO_DEVICE, "raster_create: no HIP device");
+  asciichat_raster_t *h = (asciichat_raster_t *)calloc(1, sizeof(*h));
+  /* the tables as one host block, laid out as on the device */
+  const size_t ng = (size_t)font->n_glyphs;
+  const size_t at_glyphs = round16(4u * ng), at_lut = at_glyphs + sizeof(raster_glyph_t) * ng, at_cov = at_lut + 4u * 512u;
+  const size_t bytes = at_cov + round16(font->coverage_bytes) + 16u;
+  uint8_t *host = (uint8_t *)calloc(1, bytes);
+  if (!h || !host) {
+    free(h);
+    free(host);
+    return fail(ASCIICHAT_RASTER_ERR_MEMORY, "raster_create: out of memory");
+  }
+  raster_tables(font, (uint32_t *)host, (raster_glyph_t *)(host + at_glyphs), (uint32_t *)(host + at_lut));
+  if (font->coverage_bytes)
+    memcpy(host + at_cov, font->coverage, font->coverage_bytes);
+  h->magic = RASTER_MAGIC;
+  h->max_frames = max_frames;
+  const size_t n = (size_t)max_frames, nr = (size_t)rows, nc = (size_t)cols;
+  int rc = hip_check(hipGetDevice(&h->device), "hipGetDevice");
+  if (!rc)
+    rc = hip_check(hipMalloc((void **)&h->tables, bytes), "hipMalloc(raster tables)");
+  if (!rc)
+    rc = hip_check(hipMalloc((void **)&h->starts, 4u * n * (nr + 2u)), "hipMalloc(raster row starts)");
+  if (!rc)
+    rc = hip_check(hipMalloc((void **)&h->recs, sizeof(raster_rowrec_t) * n * (nr + 1u)), "hipMalloc(raster row records)");
+  if (!rc)
+    rc = hip_check(hipMalloc((void **)&h->cells, sizeof(raster_cell_t) * n * nr * nc), "hipMalloc(raster cells)");
+  if (!rc)
+    rc = hip_check(hipMemcpy(h->tables, host, bytes, hipMemcpyHostToDevice), "hipMemcpy(raster tables)"); /* landed on return */
+  free(host);
+  if (rc) {
+    raster_free(h);
+    return rc;
+  }
+  raster_params_t *p = &h->p;
+  p->cols = cols, p->rows = rows, p->cell_w = font->cell_w, p->cell_h = font->cell_h;
+  p->n_glyphs = font->n_glyphs, p->matrix_map = font->matrix_map != 0;
+  p->default_fg = font->default_fg & 0xFFFFFFu, p->default_bg = font->default_bg & 0xFFFFFFu;
+  p->codepoints = (const uint32_t *)h->tables;
+  p->glyphs = (const raster_glyph_t *)(h->tables + at_glyphs);
+  p->lut = (const uint32_t *)(h->tables + at_lut);
+  p->coverage = h->tables + at_cov;
+  p->coverage_bytes = (uint32_t)font->coverage_bytes;
+  p->atlas_in_lds = font->coverage_bytes <= RASTER_ATLAS_LDS;
+  *r = h;
+  return 0;
+}
+
+int asciichat_raster_width_px(const asciichat_raster_t *r) {
+  const asciichat_raster_t *h = raster_of(r);
+  return h ? h->p.cols * h->p.cell_w : 0;
+}
+
+int asciichat_raster_height_px(const asciichat_raster_t *r) {
+  const asciichat_raster_t *h = raster_of(r);
+  return h ? h->p.rows * h->p.cell_h : 0;
+}
+
+size_t asciichat_raster_image_pitch(const asciichat_raster_t *r) {
+  return 4u * (size_t)asciichat_raster_width_px(r) * (size_t)asciichat_raster_height_px(r);
+}
+
+static int frames_ok(const asciichat_raster_t *h, int n, const char *what) {
+  if (!h)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: not a rasteriser", what);
+  if (n < 1 || n > h->max_frames)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: %d frames for a rasteriser of 1..%d", what, n, h->max_frames);
+  return 0;
+}
+
+int asciichat_raster_parse(asciichat_raster_t *r, const uint8_t *frames_dev, size_t frame_stride, const uint32_t *len_dev, int n,
+                           uint32_t *status_dev, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  const int rc = frames_ok(h, n, "raster_parse");
+  if (rc)
+    return rc;
+  if (!frames_dev || !len_dev || !status_dev)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_parse: frames, lengths and a status array are required");
+  if (frame_stride > 0x7FFFFFFFu) /* (byte positions in a frame are 32-bit) */
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_parse: frame stride %zu beyond 2^31 - 1", frame_stride);
+  return hip_check((hipError_t)raster_launch_parse(&h->p, frames_dev, (uint64_t)frame_stride, len_dev, n, h->starts, h->recs, h->cells,
+                                                   status_dev, stream),
+                   "raster parse launch");
+}
+
+int asciichat_raster_draw(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  const int rc = frames_ok(h, n, "raster_draw");
+  if (rc)
+    return rc;
+  if (!pixels_dev || ((uintptr_t)pixels_dev & 3u) || (image_pitch & 3u))
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_draw: 4-byte aligned pixels and image pitch are required");
+  if (image_pitch < asciichat_raster_image_pitch(h))
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_draw: pitch %zu below an image's %zu bytes", image_pitch,
+                asciichat_raster_image_pitch(h));
+  return hip_check((hipError_t)raster_launch_draw(&h->p, h->cells, n, pixels_dev, (uint64_t)image_pitch, stream), "raster draw launch");
+}
+
+int asciichat_raster_run(asciichat_raster_t *r, const uint8_t *frames_dev, size_t frame_stride, const uint32_t *len_dev, int n,
+                         uint8_t *pixels_dev, size_t image_pitch, uint32_t *status_dev, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  int rc = frames_ok(h, n, "raster_run");
+  if (rc)
+    return rc;
+  /* nothing is launched unless both stages take their arguments */
+  if (!pixels_dev || ((uintptr_t)pixels_dev & 3u) || (image_pitch & 3u) || image_pitch < asciichat_raster_image_pitch(h))
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_run: 4-byte aligned pixels and an image pitch of at least %zu are required",
+                asciichat_raster_image_pitch(h));
+  rc = asciichat_raster_parse(r, frames_dev, frame_stride, len_dev, n, status_dev, stream);
+  return rc ? rc : asciichat_raster_draw(r, n, pixels_dev, image_pitch, stream);
+}
+
+void asciichat_raster_destroy(asciichat_raster_t *r) {
+  asciichat_raster_t *h = raster_of(r);
+  if (!h)
+    return;
+  int cur = 0;
+  (void)hipGetDevice(&cur);
+  (void)hipSetDevice(h->device);
+  raster_free(h);
+  (void)hipSetDevice(cur);
+}

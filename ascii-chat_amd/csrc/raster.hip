@@ -1,0 +1,42 @@
+/* raster.hip -- the launchers of the rasteriser (raster_kernels.hpp); the host side is raster.c. */
+#include <hip/hip_runtime.h>
+
+#include "launch_common.hpp"
+#include "raster.h"
+#include "raster_kernels.hpp"
+
+extern "C" int raster_launch_parse(const raster_params_t *p, const uint8_t *frames, uint64_t frame_stride, const uint32_t *len, int n,
+                                   uint32_t *starts, raster_rowrec_t *recs, raster_cell_t *cells, uint32_t *status, void *stream) {
+  if (!p || !frames || !len || n <= 0 || !starts || !recs || !cells || !status)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned rows = (unsigned)p->rows;
+  hipLaunchKernelGGL(achip::raster::starts_kernel, dim3((unsigned)n), dim3(RASTER_BLOCK), 64, s, *p, frames, frame_stride, len, starts);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    return (int)e;
+  const unsigned bpf = (rows + 1u + RASTER_ROWS_PER_BLOCK - 1u) / RASTER_ROWS_PER_BLOCK;
+  hipLaunchKernelGGL(achip::raster::parse_kernel, dim3((unsigned)n * bpf), dim3(RASTER_BLOCK), raster_parse_lds(), s, *p, frames,
+                     frame_stride, len, starts, recs, cells);
+  e = hipGetLastError();
+  if (e != hipSuccess)
+    return (int)e;
+  const unsigned groups = (rows + RASTER_FIX_ROWS - 1u) / RASTER_FIX_ROWS;
+  hipLaunchKernelGGL(achip::raster::resolve_kernel, dim3((unsigned)n * groups), dim3(RASTER_BLOCK), (2u * RASTER_FIX_ROWS + RASTER_BLOCK) * 4u,
+                     s, *p, recs, cells, status);
+  return (int)hipGetLastError();
+}
+
+extern "C" int raster_launch_draw(const raster_params_t *p, const raster_cell_t *cells, int n, uint8_t *pixels, uint64_t image_pitch,
+                                  void *stream) {
+  if (!p || !cells || n <= 0 || !pixels)
+    return (int)hipErrorInvalidValue;
+  const int lds = (int)raster_draw_lds(p);
+  const hipError_t e = achip::ensure_dynamic_lds<achip::raster::draw_kernel>(lds);
+  if (e != hipSuccess)
+    return (int)e;
+  const unsigned tiles = (unsigned)raster_tiles(p), strips = (unsigned)n * (unsigned)p->rows, split = raster_draw_split(p, n);
+  hipLaunchKernelGGL(achip::raster::draw_kernel, dim3(strips, split), dim3(RASTER_BLOCK), (size_t)lds, static_cast<hipStream_t>(stream), *p,
+                     cells, pixels, image_pitch, tiles);
+  return (int)hipGetLastError();
+}

@@ -1,0 +1,117 @@
+/*
+ * asciichat_raster.h -- libasciichat_raster.so: rendered ANSI frames rasterised to RGBA pixels on the device, one font-cell
+ * rectangle per character, with a caller-supplied glyph atlas.  The step the reference takes in term_renderer_feed
+ * (lib/media/render/terminal.c:405-529, blit_glyph :170-193) before it encodes video.  An opt-in batch pass and NOT a parity
+ * path where DESIGN.md 7 says so: every frame starts from a default pen on a blank screen, nothing wraps or scrolls, every
+ * codepoint takes one column, and only the grammar below is interpreted.
+ *
+ * A library of its own: it needs nothing of libasciichat_hip.so and shares only achip_types.h (ACHIP_LEN_OVERFLOW) and the
+ * values of the error codes with it.
+ *
+ * Frame grammar (what this project's renderers, the rain pass and ascii_create_grid emit):
+ *   "\n", "\r\n"   column 0 of the next row;  a bare "\r": column 0
+ *   UTF-8          one codepoint = one cell, one column; a malformed sequence is U+FFFD and sets BAD_UTF8
+ *   ESC [ P.. I.. F  (P 0x30-0x3F, I 0x20-0x2F, F 0x40-0x7E) is one unit:
+ *     F == 'm' (SGR), parameters left to right: empty | 0 reset; 38;2;r;g;b / 48;2;r;g;b; 38;5;n / 48;5;n; 30-37, 90-97 indexed
+ *       fg 0-15; 40-47, 100-107 indexed bg; 39 / 49 default fg / bg; anything else is ignored and sets UNKNOWN
+ *     F == 'b' (REP): the last character written in this row n more times with the current pen (empty n = 1); at a row
+ *       start nothing, and UNKNOWN
+ *     any other F, other C0 bytes, an ESC without '[': ignored, UNKNOWN
+ *   a character at column >= cols is dropped (OVERFLOW_COLS), at row >= rows dropped (OVERFLOW_ROWS)
+ * The pen persists across the rows of a frame, not across frames.
+ *
+ * Compositing (terminal.c:468-525): cells in row-major order; each fills its rectangle with its background, alpha 255, then
+ * blits its glyph clipped to the image only -- every pixel of the bitmap rectangle becomes (f*a + b*(255-a)) / 255 per channel
+ * of the glyph's own cell's colours, those with a == 0 included.  A pixel therefore shows its last writer in that order.
+ */
+#ifndef ASCIICHAT_RASTER_H
+#define ASCIICHAT_RASTER_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "achip_types.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the values of asciichat_hip.h's codes of the same names */
+enum {
+  ASCIICHAT_RASTER_OK = 0,
+  ASCIICHAT_RASTER_ERR_MEMORY = 3,
+  ASCIICHAT_RASTER_ERR_INVALID_PARAM = 86,
+  ASCIICHAT_RASTER_ERR_NO_DEVICE = 200 /* no HIP device, or a HIP runtime failure */
+};
+
+/* status_dev[i]: the OR of these; 0 = a frame the grammar covers fully */
+#define ASCIICHAT_RASTER_NO_FRAME 1u      /* len_dev[i] was ACHIP_LEN_OVERFLOW (or beyond frame_stride): a blank image */
+#define ASCIICHAT_RASTER_BAD_UTF8 2u
+#define ASCIICHAT_RASTER_UNKNOWN 4u
+#define ASCIICHAT_RASTER_OVERFLOW_COLS 8u
+#define ASCIICHAT_RASTER_OVERFLOW_ROWS 16u
+
+#define ASCIICHAT_RASTER_INDEXED_FLAT 1  /* every indexed colour is flat_fg / flat_bg (the reference, terminal.c:474-488) */
+#define ASCIICHAT_RASTER_INDEXED_XTERM 2 /* 0-15 get_16color_rgb, 16-231 the 0,95,135,175,215,255 cube, 232-255 8 + 10 k */
+
+#define ASCIICHAT_RASTER_MAX_COLS 1024
+#define ASCIICHAT_RASTER_MAX_ROWS 512
+#define ASCIICHAT_RASTER_MAX_FRAMES 4096
+#define ASCIICHAT_RASTER_MAX_GLYPHS 1024
+#define ASCIICHAT_RASTER_MAX_COVERAGE (1u << 20)
+#define ASCIICHAT_RASTER_MAX_CELL_W 32
+#define ASCIICHAT_RASTER_MAX_CELL_H 64
+
+/* One glyph: FreeType's bitmap_left / bitmap_top / bitmap.width / .rows / .pitch, its 8-bit coverage at coverage + offset.
+ * Relative to its cell's origin the bitmap covers x0 = left, y0 = baseline - top, x1 = x0 + width, y1 = y0 + rows, which must
+ * lie within [-cell_w, 2 cell_w] x [-cell_h, 2 cell_h]; pitch >= width; offset + pitch * rows <= coverage_bytes. */
+typedef struct {
+  uint32_t codepoint;
+  int16_t left, top;
+  uint16_t width, rows;
+  uint32_t pitch, offset;
+} asciichat_raster_glyph_t;
+
+typedef struct {
+  int32_t cell_w, cell_h, baseline;       /* 1..32, 1..64, 0..cell_h */
+  int32_t n_glyphs;                       /* 0..1024, codepoints strictly ascending */
+  const asciichat_raster_glyph_t *glyphs; /* host */
+  const uint8_t *coverage;                /* host, 8-bit alpha */
+  size_t coverage_bytes;                  /* <= 1 MB */
+  uint32_t default_fg, default_bg;        /* 0x00RRGGBB */
+  int32_t indexed;                        /* ASCIICHAT_RASTER_INDEXED_FLAT | _XTERM, no default */
+  uint32_t flat_fg, flat_bg;              /* FLAT: every indexed colour (reference: 204,204,204 / theme 0 or 255) */
+  int32_t matrix_map;                     /* apply matrix_char_map (terminal.c:146-165) before the atlas lookup */
+} asciichat_raster_font_t;
+
+typedef struct asciichat_raster asciichat_raster_t;
+
+/* Number of HIP devices (0 when there is none or the runtime fails). */
+int asciichat_raster_device_count(void);
+/* Message of the calling thread's last failed call ("" when none). */
+const char *asciichat_raster_last_error(void);
+
+/* A rasteriser of cols x rows cell frames (1..1024 x 1..512), up to max_frames (1..4096) per run, on the current device.
+ * Everything is validated before a device is needed (ERR_INVALID_PARAM), then ERR_NO_DEVICE without one.  The atlas is copied
+ * to the device; all scratch of run() is allocated here. */
+int asciichat_raster_create(asciichat_raster_t **r, const asciichat_raster_font_t *font, int cols, int rows, int max_frames);
+int asciichat_raster_width_px(const asciichat_raster_t *r);     /* cols * cell_w */
+int asciichat_raster_height_px(const asciichat_raster_t *r);    /* rows * cell_h */
+size_t asciichat_raster_image_pitch(const asciichat_raster_t *r); /* 4 * width * height: bytes of one image, rows tight */
+
+/* Frames as asciichat_hip_plan_render leaves them: frame i at frames_dev + i * frame_stride (< 2^31), len_dev[i] bytes.  Image i goes to
+ * pixels_dev + i * image_pitch (4-byte aligned both, image_pitch >= the image's bytes): R, G, B, 255 per pixel, rows 4 * width
+ * bytes apart; nothing else is written.  status_dev[i]: the flags above.  1 <= n <= max_frames.  Asynchronous on `stream`:
+ * never synchronises, allocates nothing. */
+int asciichat_raster_run(asciichat_raster_t *r, const uint8_t *frames_dev, size_t frame_stride, const uint32_t *len_dev, int n,
+                         uint8_t *pixels_dev, size_t image_pitch, uint32_t *status_dev, void *stream);
+/* run()'s two stages on their own (timing): parse fills the handle's cell grids, raster draws them. */
+int asciichat_raster_parse(asciichat_raster_t *r, const uint8_t *frames_dev, size_t frame_stride, const uint32_t *len_dev, int n,
+                           uint32_t *status_dev, void *stream);
+int asciichat_raster_draw(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, void *stream);
+void asciichat_raster_destroy(asciichat_raster_t *r);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
