@@ -673,33 +673,6 @@ class Plan:
         if rc != 0:
             raise RuntimeError(f"plan_render_packets_packed failed ({rc}): {last_error()}")
 
-    def render_packets_zpacked(self, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity,
-                               off_ptr, len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
-        """render + the wire stage with the frames compressed for the wire (asciichat_hip_plan_render_packets_zpacked)"""
-        rc = _bind_zpack(lib()).asciichat_hip_plan_render_packets_zpacked(self._h, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr,
-                                                                          hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
-                                                                          len_out_ptr, scratch_ptr, scratch_bytes, stream)
-        if rc != 0:
-            raise RuntimeError(f"plan_render_packets_zpacked failed ({rc}): {last_error()}")
-
-    def render_packets_zpacked_wide(self, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity,
-                                    off_ptr, len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
-        """render + the wide form of that stage (asciichat_hip_plan_render_packets_zpacked_wide; zpack_wide_scratch_bytes)"""
-        rc = _bind_zpack(lib()).asciichat_hip_plan_render_packets_zpacked_wide(self._h, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr,
-                                                                               hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
-                                                                               len_out_ptr, scratch_ptr, scratch_bytes, stream)
-        if rc != 0:
-            raise RuntimeError(f"plan_render_packets_zpacked_wide failed ({rc}): {last_error()}")
-
-    def render_packets_zpacked_seq(self, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity,
-                                   off_ptr, len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
-        """render + the sequence form of that stage (asciichat_hip_plan_render_packets_zpacked_seq; zpack_seq_scratch_bytes)"""
-        rc = _bind_zpack(lib()).asciichat_hip_plan_render_packets_zpacked_seq(self._h, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr,
-                                                                              hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
-                                                                              len_out_ptr, scratch_ptr, scratch_bytes, stream)
-        if rc != 0:
-            raise RuntimeError(f"plan_render_packets_zpacked_seq failed ({rc}): {last_error()}")
-
     def set_fused_crc(self, mode):
         """-1 automatic (fused where it is the faster form), 0 never, 1 wherever the geometry carries it"""
         rc = lib().asciichat_hip_plan_set_fused_crc(self._h, mode)
@@ -806,52 +779,50 @@ def _bind_zpack(L):
     return L
 
 
-def zpack_scratch_bytes(max_len, n):
-    """bytes of device scratch a zpacked call over n frames of up to max_len bytes needs"""
-    return int(_bind_zpack(lib()).asciichat_hip_zpack_scratch_bytes(max_len, n))
+def _zpack_form(suffix, scratch_doc, frame_doc, plan_doc):
+    """the three callables of one zpacked form: zpack<suffix>_scratch_bytes, frame_packets_zpacked<suffix> and
+    Plan.render_packets_zpacked<suffix>"""
+    def scratch_bytes(max_len, n):
+        return int(getattr(_bind_zpack(lib()), f"asciichat_hip_zpack{suffix}_scratch_bytes")(max_len, n))
+
+    def frame_packets(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                      len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+        fn = getattr(_bind_zpack(lib()), f"asciichat_hip_frame_packets_zpacked{suffix}")
+        rc = fn(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr, len_out_ptr,
+                scratch_ptr, scratch_bytes, stream)
+        if rc != 0:
+            raise RuntimeError(f"frame_packets_zpacked{suffix} failed ({rc}): {last_error()}")
+
+    def render_packets(self, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
+                       len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
+        fn = getattr(_bind_zpack(lib()), f"asciichat_hip_plan_render_packets_zpacked{suffix}")
+        rc = fn(self._h, slab_ptr, out_stride, len_ptr, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr, len_out_ptr,
+                scratch_ptr, scratch_bytes, stream)
+        if rc != 0:
+            raise RuntimeError(f"plan_render_packets_zpacked{suffix} failed ({rc}): {last_error()}")
+
+    for fn, name, doc in ((scratch_bytes, f"zpack{suffix}_scratch_bytes", scratch_doc),
+                          (frame_packets, f"frame_packets_zpacked{suffix}", frame_doc),
+                          (render_packets, f"render_packets_zpacked{suffix}", plan_doc)):
+        fn.__name__, fn.__doc__ = name, doc
+        fn.__qualname__ = name if fn is not render_packets else "Plan." + name
+    globals()[scratch_bytes.__name__] = scratch_bytes
+    globals()[frame_packets.__name__] = frame_packets
+    setattr(Plan, render_packets.__name__, render_packets)
 
 
-def frame_packets_zpacked(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
-                          len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
-    """asciichat_hip_frame_packets_zpacked: the wire stage with the frames compressed on the device where the sender's rule
-    says so (zstd frames of raw / RLE / Huffman-literals blocks), pack_frames' layout over the sent lengths; asynchronous"""
-    rc = _bind_zpack(lib()).asciichat_hip_frame_packets_zpacked(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr,
-                                                                dst_ptr, dst_capacity, off_ptr, len_out_ptr, scratch_ptr, scratch_bytes,
-                                                                stream)
-    if rc != 0:
-        raise RuntimeError(f"frame_packets_zpacked failed ({rc}): {last_error()}")
-
-
-def zpack_wide_scratch_bytes(max_len, n):
-    """bytes of device scratch a zpacked_wide call over n frames of up to max_len bytes needs"""
-    return int(_bind_zpack(lib()).asciichat_hip_zpack_wide_scratch_bytes(max_len, n))
-
-
-def frame_packets_zpacked_wide(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
-                               len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
-    """asciichat_hip_frame_packets_zpacked_wide: frame_packets_zpacked over all 256 byte values (half-block frames and
-    multi-byte palettes are coded too: the tree in zstd's FSE-compressed form); scratch of zpack_wide_scratch_bytes"""
-    rc = _bind_zpack(lib()).asciichat_hip_frame_packets_zpacked_wide(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr,
-                                                                     pkt_ptr, dst_ptr, dst_capacity, off_ptr, len_out_ptr, scratch_ptr,
-                                                                     scratch_bytes, stream)
-    if rc != 0:
-        raise RuntimeError(f"frame_packets_zpacked_wide failed ({rc}): {last_error()}")
-
-
-def zpack_seq_scratch_bytes(max_len, n):
-    """bytes of device scratch a zpacked_seq call over n frames of up to max_len bytes needs"""
-    return int(_bind_zpack(lib()).asciichat_hip_zpack_seq_scratch_bytes(max_len, n))
-
-
-def frame_packets_zpacked_seq(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr, pkt_ptr, dst_ptr, dst_capacity, off_ptr,
-                              len_out_ptr, scratch_ptr, scratch_bytes, stream=0):
-    """asciichat_hip_frame_packets_zpacked_seq: frame_packets_zpacked_wide with the matches of a 64-byte window coded as zstd
-    sequences under the predefined tables, one block per 8192 bytes; scratch of zpack_seq_scratch_bytes"""
-    rc = _bind_zpack(lib()).asciichat_hip_frame_packets_zpacked_seq(base_ptr, stride, len_ptr, max_len, n, dims_ptr, crc_ptr, hdr_ptr,
-                                                                    pkt_ptr, dst_ptr, dst_capacity, off_ptr, len_out_ptr, scratch_ptr,
-                                                                    scratch_bytes, stream)
-    if rc != 0:
-        raise RuntimeError(f"frame_packets_zpacked_seq failed ({rc}): {last_error()}")
+_zpack_form("", "bytes of device scratch a zpacked call over n frames of up to max_len bytes needs",
+            """asciichat_hip_frame_packets_zpacked: the wire stage with the frames compressed on the device where the sender's rule
+    says so (zstd frames of raw / RLE / Huffman-literals blocks), pack_frames' layout over the sent lengths; asynchronous""",
+            "render + the wire stage with the frames compressed for the wire (asciichat_hip_plan_render_packets_zpacked)")
+_zpack_form("_wide", "bytes of device scratch a zpacked_wide call over n frames of up to max_len bytes needs",
+            """asciichat_hip_frame_packets_zpacked_wide: frame_packets_zpacked over all 256 byte values (half-block frames and
+    multi-byte palettes are coded too: the tree in zstd's FSE-compressed form); scratch of zpack_wide_scratch_bytes""",
+            "render + the wide form of that stage (asciichat_hip_plan_render_packets_zpacked_wide; zpack_wide_scratch_bytes)")
+_zpack_form("_seq", "bytes of device scratch a zpacked_seq call over n frames of up to max_len bytes needs",
+            """asciichat_hip_frame_packets_zpacked_seq: frame_packets_zpacked_wide with the matches of a 64-byte window coded as zstd
+    sequences under the predefined tables, one block per 8192 bytes; scratch of zpack_seq_scratch_bytes""",
+            "render + the sequence form of that stage (asciichat_hip_plan_render_packets_zpacked_seq; zpack_seq_scratch_bytes)")
 
 
 class HostBuffer:

@@ -102,20 +102,15 @@ static inline size_t achip_zseq_scratch_bytes(uint32_t max_len, int n) {
   return (size_t)n * ((size_t)achip_zseq_pieces(max_len) * (4u * ACHIP_ZSEQ_REC_WORDS + achip_zseq_slot_bytes(max_len)) + 4u * ACHIP_ZPACK_FRM_WORDS);
 }
 
-/* frames i < n at base + i * stride, len_dev[i] bytes each (<= max_len): see asciichat_hip_frame_packets_zpacked.  Returns a
- * hipError_t. */
-int achip_launch_zpack(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
-                       uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
-                       uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
-/* the same over all 256 byte values (asciichat_hip_frame_packets_zpacked_wide); scratch: achip_zpack_wide_scratch_bytes */
-int achip_launch_zpack_wide(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
-                            uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
-                            uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
-
-/* the sequence form (asciichat_hip_frame_packets_zpacked_seq); scratch: achip_zseq_scratch_bytes */
-int achip_launch_zseq(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
-                      uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
-                      uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
+/* a form's launcher: frames i < n at base + i * stride, len_dev[i] bytes each (<= max_len): see
+ * asciichat_hip_frame_packets_zpacked.  Returns a hipError_t. */
+typedef int achip_zpack_launch_fn(const uint8_t *base, uint64_t stride, const uint32_t *len_dev, uint32_t max_len, int n, const uint32_t *dims_dev,
+                                  uint32_t *crc_out, uint8_t *hdr_out, uint32_t *pkt_crc_out, uint8_t *dst, uint64_t dst_capacity,
+                                  uint64_t *off_out, uint32_t *len_out, uint32_t *scratch, void *stream);
+achip_zpack_launch_fn achip_launch_zpack;      /* the narrow form; scratch: achip_zpack_scratch_bytes */
+achip_zpack_launch_fn achip_launch_zpack_wide; /* the same over all 256 byte values (asciichat_hip_frame_packets_zpacked_wide); scratch:
+                                                  achip_zpack_wide_scratch_bytes */
+achip_zpack_launch_fn achip_launch_zseq;       /* the sequence form (asciichat_hip_frame_packets_zpacked_seq); scratch: achip_zseq_scratch_bytes */
 
 #ifdef __cplusplus
 }

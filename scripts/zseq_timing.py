@@ -11,9 +11,7 @@ Usage: zseq_timing.py [--frames 256] [--reps 30] [--out profiles/zseq_timing.txt
 """
 import argparse
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
@@ -21,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import wire_timing as WT  # noqa: E402
 
 # name, plan mode, the oracle's colour level and render mode, source w x h, output w x h
 SHAPES = [("truecolor-fg 1080p->80x24", 1, 3, 0, 1920, 1080, 80, 24),
@@ -28,7 +27,7 @@ SHAPES = [("truecolor-fg 1080p->80x24", 1, 3, 0, 1920, 1080, 80, 24),
           ("ANSI-256 fg 1080p->80x24", 2, 2, 0, 1920, 1080, 80, 24),
           ("half-block truecolor 1080p->80x24", 5, 3, 2, 1920, 1080, 80, 24),
           ("half-block truecolor sampled 400x240->400x120", 5, 3, 2, 400, 240, 400, 120)]
-DISTINCT = 16
+DISTINCT = WT.DISTINCT
 
 
 def sources(orc, kind, sw, sh):
@@ -81,104 +80,30 @@ def main():
     import zseq_ref as S
 
     pkg = load_package()
-    lib = pkg.lib()
-    assert torch.cuda.is_available() and lib.asciichat_hip_device_count() > 0, "needs a GPU"
+    assert torch.cuda.is_available() and pkg.lib().asciichat_hip_device_count() > 0, "needs a GPU"
     n = args.frames
     lines = [f"# scripts/zseq_timing.py: {n} frames per launch, {args.reps} launches per figure (median), destination = mapped host memory",
              f"# {torch.cuda.get_device_name(0)}; libzstd {'loaded' if Z.libzstd() is not None else 'absent'}; blocks of {S.PIECE} bytes"]
-    big = torch.zeros(64 << 20, dtype=torch.uint8, device="cuda")
-    pinned = torch.zeros(64 << 20, dtype=torch.uint8).pin_memory()
-    ts = []
-    for _ in range(10):  # the PCIe rate a device -> pinned host copy reaches (64 MB, median of 10)
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        pinned.copy_(big, non_blocking=True)
-        b.record()
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b) * 1e-3)
-    rate = (64 << 20) / statistics.median(ts)
+    rate = WT.pcie_rate()
     lines.append(f"# measured device -> pinned host copy: {rate / 1e9:.1f} GB/s")
-    del big, pinned
     print("\n".join(lines), flush=True)
 
     streams = [torch.cuda.Stream() for _ in range(4)]
     for k in args.shapes:
         name, mode, _, rm, sw, sh, ow, oh = SHAPES[k]
         for kind in args.inputs:
-            dev = torch.from_numpy(np.stack(sources(orc, kind, sw, sh))).cuda()
-            fs = [pkg.frame_setup(dev.data_ptr() + (i % DISTINCT) * sw * sh * 3, sw, sh, ow, oh, rm, False, False, False) for i in range(n)]
-            plan = pkg.Plan(mode, orc.PALETTE_STANDARD, fs)
-            stride = plan.stride
-            slab = torch.zeros(n * stride + 16, dtype=torch.uint8, device="cuda")
-            ln = torch.zeros(n, dtype=torch.int32, device="cuda")
-            plan.render(slab.data_ptr(), stride, ln.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-            lens = ln.cpu().numpy().view(np.uint32)
-            original = int(lens.sum())
-            cap = int(((lens.astype(np.int64) + 15) // 16 * 16).sum()) + 4096
-            d = torch.from_numpy(np.array([(ow, oh)] * n, dtype=np.uint32).view(np.int32)).cuda()
-            sbytes = max(pkg.zpack_seq_scratch_bytes(stride, n), pkg.zpack_wide_scratch_bytes(stride, n))
-
-            def buffers():
-                return dict(host=pkg.HostBuffer(cap), off=torch.zeros(n + 1, dtype=torch.int64, device="cuda"),
-                            lo=torch.zeros(n, dtype=torch.int32, device="cuda"), crc=torch.zeros(n, dtype=torch.int32, device="cuda"),
-                            pkt=torch.zeros(n, dtype=torch.int32, device="cuda"), hdr=torch.zeros(24 * n, dtype=torch.uint8, device="cuda"),
-                            scratch=torch.zeros(sbytes // 8 + 1, dtype=torch.int64, device="cuda"))
-
-            bufs = [buffers() for _ in range(4)]
-
-            def packed(b, s):
-                rc = lib.asciichat_hip_frame_packets_packed(slab.data_ptr(), stride, ln.data_ptr(), stride, n, d.data_ptr(), b["crc"].data_ptr(),
-                                                            b["hdr"].data_ptr(), b["pkt"].data_ptr(), b["host"].dev, cap, b["off"].data_ptr(),
-                                                            b["lo"].data_ptr(), s)
-                assert rc == 0, pkg.last_error()
-
-            def form(fn):
-                def run(b, s):
-                    fn(slab.data_ptr(), stride, ln.data_ptr(), stride, n, d.data_ptr(), b["crc"].data_ptr(), b["hdr"].data_ptr(), b["pkt"].data_ptr(),
-                       b["host"].dev, cap, b["off"].data_ptr(), b["lo"].data_ptr(), b["scratch"].data_ptr(), sbytes, s)
-                return run
-
-            wide, seq = form(pkg.frame_packets_zpacked_wide), form(pkg.frame_packets_zpacked_seq)
-
-            def one_at_a_time(fn):
-                s = torch.cuda.current_stream().cuda_stream
-                ts = []
-                for r in range(args.reps + 3):
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    fn(bufs[0], s)
-                    b.record()
-                    torch.cuda.synchronize()
-                    if r >= 3:
-                        ts.append(a.elapsed_time(b) * 1e3)
-                return statistics.median(ts)
-
-            def four_in_flight(fn):
-                ts = []
-                for r in range(args.reps // 3 + 2):
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    for _ in range(4):
-                        for b, st in zip(bufs, streams):
-                            fn(b, st.cuda_stream)
-                    torch.cuda.synchronize()
-                    if r >= 2:
-                        ts.append((time.perf_counter() - t0) * 1e6 / 16)
-                return statistics.median(ts)
-
-            t1 = {w: one_at_a_time(fn) for w, fn in (("packed", packed), ("wide", wide), ("seq", seq))}
-            t4 = {w: four_in_flight(fn) for w, fn in (("packed", packed), ("wide", wide), ("seq", seq))}
-            host_slab = slab.cpu().numpy()
-            frames = [host_slab[i * stride:i * stride + int(lens[i])].tobytes() for i in range(min(n, DISTINCT))]
+            batch = WT.Batch(pkg, orc.PALETTE_STANDARD, sources(orc, kind, sw, sh), mode, rm, ow, oh, n, args.reps, streams)
+            batch.buffers(max(pkg.zpack_seq_scratch_bytes(batch.stride, n), pkg.zpack_wide_scratch_bytes(batch.stride, n)))
+            stride, lens, original = batch.stride, batch.lens, batch.original
+            packed, wide, seq = batch.packed, batch.form(pkg.frame_packets_zpacked_wide), batch.form(pkg.frame_packets_zpacked_seq)
+            t1 = {w: batch.one_at_a_time(fn)[0] for w, fn in (("packed", packed), ("wide", wide), ("seq", seq))}
+            t4 = {w: batch.four_in_flight(fn) for w, fn in (("packed", packed), ("wide", wide), ("seq", seq))}
+            frames = batch.frames(DISTINCT)
             sent = {}
             for w, fn in (("wide", wide), ("seq", seq)):
-                fn(bufs[0], torch.cuda.current_stream().cuda_stream)
-                torch.cuda.synchronize()
-                sent_len = bufs[0]["lo"].cpu().numpy().view(np.uint32)
+                sent_len, offs, view = batch.sent(fn)
                 sent[w] = (int(sent_len.sum()), int((sent_len != lens).sum()))
                 if w == "seq":  # what was sent is what the restatement sends, and libzstd decodes it
-                    offs, view = bufs[0]["off"].cpu().numpy(), bufs[0]["host"].view()
                     for i in (0, len(frames) - 1):
                         payload = view[int(offs[i]):int(offs[i]) + int(sent_len[i])].tobytes()
                         assert payload == S.wire(frames[i])[0], f"{name}: frame {i} differs from the restatement"
@@ -193,16 +118,13 @@ def main():
                      f"  four in flight       : zpacked_seq {t4['seq']:8.1f} us   zpacked_wide {t4['wide']:8.1f} us   packed {t4['packed']:8.1f} us   "
                      f"(wall clock per launch)"]
             for w, label in (("seq", "zseq"), ("wide", "wide")):
-                lhs1, rhs1 = t1[w] + sent[w][0] / rate * 1e6, t1["packed"] + original / rate * 1e6
-                lhs4, rhs4 = t4[w] + sent[w][0] / rate * 1e6, t4["packed"] + original / rate * 1e6
-                block.append(f"  {label} pays for itself against packed: one at a time {lhs1:8.1f} us < {rhs1:8.1f} us ? {'YES' if lhs1 < rhs1 else 'NO'}   "
-                             f"four in flight {lhs4:8.1f} us < {rhs4:8.1f} us ? {'YES' if lhs4 < rhs4 else 'NO'}")
+                lhs1, rhs1, yes1 = WT.pays(t1[w], sent[w][0], t1["packed"], original, rate)
+                lhs4, rhs4, yes4 = WT.pays(t4[w], sent[w][0], t4["packed"], original, rate)
+                block.append(f"  {label} pays for itself against packed: one at a time {lhs1:8.1f} us < {rhs1:8.1f} us ? {yes1}   "
+                             f"four in flight {lhs4:8.1f} us < {rhs4:8.1f} us ? {yes4}")
             lines += block
             print("\n".join(block), flush=True)
-            for b in bufs:
-                b["host"].close()
-            plan.close()
-            del dev, slab, bufs
+            batch.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

@@ -2,13 +2,12 @@
 and the scenes the emulated and the GPU tests share -- sources, the composite descriptor over them (achip_composite_setup of
 the product library, or filled by hand), the geometry that setup is expected to give, the averaged sizes to run.  TESTS ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import box_comp_ref as CR
 import box_support as BS
+import emubuild
 
 
 class CompSrc(C.Structure):  # achip_comp_src_t (include/achip_types.h)
@@ -30,17 +29,7 @@ _lib = None
 def emulator():
     global _emu
     if _emu is None:
-        drv = os.path.join(BS.EMU_DIR, "box_comp_emu_driver.cpp")
-        srcs = [drv, os.path.join(BS.EMU_DIR, "hip_emu.h"), os.path.join(BS.EMU_DIR, "gfx950_ops.hpp"),
-                os.path.join(BS.CSRC, "box_kernels.hpp"), os.path.join(BS.CSRC, "box.h"), os.path.join(BS.INC, "achip_types.h")]
-        so = os.path.join(BS.OUT_DIR, "libbox_comp_emu.so")
-        if not BS._fresh(so, srcs):
-            os.makedirs(BS.OUT_DIR, exist_ok=True)
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-I" + BS.EMU_DIR, "-I" + BS.CSRC, "-I" + BS.INC,
-                                   drv, "-o", tmp])
-            os.replace(tmp, so)
-        L = C.CDLL(so)
+        L = C.CDLL(emubuild.shared_library("libbox_comp_emu.so", "box_comp_emu_driver.cpp", ("box_kernels.hpp", "box.h", "achip_types.h")))
         L.emu_box_composites.restype = C.c_int
         L.emu_box_composites.argtypes = [C.POINTER(BS.Frame), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_int)]

@@ -2,18 +2,13 @@
 source buffers, and the cases the emulated and the GPU tests share.  TESTS ONLY."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 import box_ref as BR
+import emubuild
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ascii-chat_amd", "csrc")
-INC = os.path.join(ROOT, "include")
-EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
-OUT_DIR = os.path.join(EMU_DIR, "_build")
-LIB = os.path.join(ROOT, "ascii-chat_amd", "libasciichat_hip.so")
+LIB = os.path.join(emubuild.ROOT, "ascii-chat_amd", "libasciichat_hip.so")
 FLIP_X, FLIP_Y = 1, 2
 FILL = 0xEE   # every image slot before the pass
 GUARD = 0xA5  # around and between the rows of a source
@@ -25,27 +20,13 @@ class Frame(C.Structure):  # achip_frame_t (include/achip_types.h)
                 ("x_ratio", C.c_uint32), ("y_ratio", C.c_uint32), ("src_stride", C.c_int32), ("ops", C.c_uint32)]
 
 
-def _fresh(out, srcs):
-    return os.path.exists(out) and all(os.path.getmtime(s) <= os.path.getmtime(out) for s in srcs)
-
-
 _emu = None
 
 
 def emulator():
     global _emu
     if _emu is None:
-        drv = os.path.join(EMU_DIR, "box_emu_driver.cpp")
-        srcs = [drv, os.path.join(EMU_DIR, "hip_emu.h"), os.path.join(EMU_DIR, "gfx950_ops.hpp"),
-                os.path.join(CSRC, "box_kernels.hpp"), os.path.join(CSRC, "box.h"), os.path.join(INC, "achip_types.h")]
-        so = os.path.join(OUT_DIR, "libbox_emu.so")
-        if not _fresh(so, srcs):
-            os.makedirs(OUT_DIR, exist_ok=True)
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-I" + EMU_DIR, "-I" + CSRC, "-I" + INC, drv,
-                                   "-o", tmp])
-            os.replace(tmp, so)
-        L = C.CDLL(so)
+        L = C.CDLL(emubuild.shared_library("libbox_emu.so", "box_emu_driver.cpp", ("box_kernels.hpp", "box.h", "achip_types.h")))
         L.emu_box.restype = C.c_int
         L.emu_box.argtypes = [C.POINTER(Frame), C.c_int, C.c_void_p, C.c_uint64, C.c_int]
         _emu = L

@@ -2,17 +2,13 @@
 guard-filled pixel buffers, and the case table the emulated and the GPU tests share.  TESTS ONLY."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import emubuild
 import raster_ref as RR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ascii-chat_amd", "csrc")
-INC = os.path.join(ROOT, "include")
-EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
-OUT_DIR = os.path.join(EMU_DIR, "_build")
+ROOT = emubuild.ROOT
 LIB = os.path.join(ROOT, "ascii-chat_amd", "libasciichat_raster.so")
 HIP_LIB = os.path.join(ROOT, "ascii-chat_amd", "libasciichat_hip.so")
 FILL = 0xEE  # every pixel byte before the pass (box_support's guard-fill idiom)
@@ -45,28 +41,14 @@ def c_font(font, cls=CFont, glyph_cls=CGlyph):
     return f
 
 
-def _fresh(out, srcs):
-    return os.path.exists(out) and all(os.path.getmtime(s) <= os.path.getmtime(out) for s in srcs)
-
-
 _emu = None
 
 
 def emulator():
     global _emu
     if _emu is None:
-        drv = os.path.join(EMU_DIR, "raster_emu_driver.cpp")
-        srcs = [drv, os.path.join(EMU_DIR, "hip_emu.h"), os.path.join(EMU_DIR, "gfx950_ops.hpp"),
-                os.path.join(CSRC, "raster_kernels.hpp"), os.path.join(CSRC, "raster.h"), os.path.join(INC, "asciichat_raster.h"),
-                os.path.join(INC, "achip_types.h")]
-        so = os.path.join(OUT_DIR, "libraster_emu.so")
-        if not _fresh(so, srcs):
-            os.makedirs(OUT_DIR, exist_ok=True)
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-I" + EMU_DIR, "-I" + CSRC, "-I" + INC, drv,
-                                   "-o", tmp])
-            os.replace(tmp, so)
-        L = C.CDLL(so)
+        L = C.CDLL(emubuild.shared_library("libraster_emu.so", "raster_emu_driver.cpp",
+                                           ("raster_kernels.hpp", "raster.h", "asciichat_raster.h", "achip_types.h")))
         L.emu_raster_chunk.restype = C.c_int
         L.emu_raster.restype = C.c_int
         L.emu_raster.argtypes = [C.POINTER(CFont), C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p,

@@ -4,6 +4,7 @@ libzstd where it loads, headers as the reference's receiver checks them, two cal
 and three pieces, plan_render_packets_zpacked over real renders, and every family of tests/zpack_cases.py -- the pass at
 its block, stream and batch boundaries -- at the real piece size, a few batches per test.  Out of scope: offsets above 4 GB
 (ZF_OFF_HI), which would have to move more than 4 GB, and lengths above max_len, which the caller promises."""
+import functools
 import os
 import struct
 import sys
@@ -18,6 +19,7 @@ import orc  # noqa: E402
 import zhuf_ref as Z  # noqa: E402
 import zpack_cases as ZC  # noqa: E402
 import zpack_support as ZS  # noqa: E402
+import zwire as ZW  # noqa: E402
 
 CASES = ZS.small_cases()
 
@@ -38,49 +40,7 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-class _Call:
-    """the buffers of one call; dst in device memory or in mapped host memory"""
-
-    def __init__(self, pkg, frames, dims, capacity=None, host=False, tail=256, stride=None):
-        import torch
-        self.pkg, self.frames, self.dims, self.n = pkg, frames, dims, len(frames)
-        slab, self.stride, ln, self.mx = ZS.slab_of(frames, stride)
-        self.slab = torch.from_numpy(np.concatenate([slab, np.full(16, ZS.FILL, dtype=np.uint8)])).cuda()
-        self.len = torch.from_numpy(ln.view(np.int32)).cuda()
-        self.len_before = ln
-        _, total = ZS.expect(frames, dims)
-        self.cap = total if capacity is None else capacity
-        self.nbytes = max(self.cap, total) + tail
-        self.host = pkg.HostBuffer(self.nbytes) if host else None
-        if host:
-            self.host.view()[:] = ZS.FILL
-            self.dst_ptr = self.host.dev
-        else:
-            self.dst = torch.full((self.nbytes,), ZS.FILL, dtype=torch.uint8, device="cuda")
-            self.dst_ptr = self.dst.data_ptr()
-        n = self.n
-        self.off = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
-        self.len_out = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-        self.crc = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-        self.pkt = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-        self.hdr = torch.full((24 * n,), ZS.FILL, dtype=torch.uint8, device="cuda")
-        self.d = torch.from_numpy(np.array(dims, dtype=np.uint32).reshape(n, 2).view(np.int32)).cuda()
-        self.sbytes = pkg.zpack_scratch_bytes(self.mx, n)
-        self.scratch = torch.zeros(self.sbytes // 8 + 1, dtype=torch.int64, device="cuda")
-
-    def launch(self, stream):
-        self.pkg.frame_packets_zpacked(self.slab.data_ptr(), self.stride, self.len.data_ptr(), self.mx, self.n, self.d.data_ptr(),
-                                       self.crc.data_ptr(), self.hdr.data_ptr(), self.pkt.data_ptr(), self.dst_ptr, self.cap,
-                                       self.off.data_ptr(), self.len_out.data_ptr(), self.scratch.data_ptr(), self.sbytes, stream)
-
-    def check(self, what):
-        dst = self.host.view().copy() if self.host else self.dst.cpu().numpy()
-        out = dict(dst=dst, off=self.off.cpu().numpy().view(np.uint64), len_out=self.len_out.cpu().numpy().view(np.uint32),
-                   crc=self.crc.cpu().numpy().view(np.uint32), hdr=self.hdr.cpu().numpy(), pkt=self.pkt.cpu().numpy().view(np.uint32))
-        ZS.check(self.frames, self.dims, out, self.cap, what)
-        assert np.array_equal(self.len.cpu().numpy().view(np.uint32), self.len_before), "len_dev keeps the original lengths"
-        if self.host:
-            self.host.close()
+_Call = functools.partial(ZW.Call, ZW.NARROW)
 
 
 @pytest.mark.parametrize("host", [False, True], ids=["device", "mapped host"])
@@ -206,9 +166,7 @@ def _once(pkg, frames, what, **kw):
     c = _Call(pkg, frames, ZS.dims_of(len(frames)), **kw)
     c.launch(_stream())
     torch.cuda.synchronize()
-    records = dict(scratch=c.scratch.cpu().numpy().view(np.uint32), pieces=max(1, -(-c.mx // Z.PIECE)))
-    c.check(what)
-    return records
+    return c.check(what)
 
 
 def test_tail_lengths_gains_and_symbols_behind_a_full_piece(pkg):

@@ -1,13 +1,11 @@
 """The zhuf wire pass without a GPU: its four kernels under the CPU emulator against the restatement (tests/zhuf_ref.py) and
 the oracle's CRC -- destination, offsets, sent lengths, headers, checksums and packet checksums byte for byte, nothing stored
 outside the frames -- and what the product library decides before it needs a device."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
 import zhuf_ref as Z
 import zpack_support as ZS
+import zwire as ZW
 
 CASES = ZS.small_cases()
 
@@ -64,34 +62,8 @@ def test_one_frame_alone_and_a_batch_of_equal_frames():
 
 
 def test_library_refuses_before_it_needs_a_device_and_needs_one_after():
-    L = C.CDLL(ZS.LIB)
-    vp, sz, u32, ci = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int
-    L.asciichat_hip_zpack_scratch_bytes.restype = sz
-    L.asciichat_hip_zpack_scratch_bytes.argtypes = [u32, ci]
-    L.asciichat_hip_frame_packets_zpacked.restype = ci
-    L.asciichat_hip_frame_packets_zpacked.argtypes = [vp, sz, vp, u32, ci, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
-    L.asciichat_hip_plan_render_packets_zpacked.restype = ci
-    L.asciichat_hip_plan_render_packets_zpacked.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
-    L.asciichat_hip_device_count.restype = ci
-    NO_DEVICE, INVALID = 200, 86
-    assert L.asciichat_hip_zpack_scratch_bytes(0, 4) == 0 and L.asciichat_hip_zpack_scratch_bytes(100, 0) == 0
-    one = L.asciichat_hip_zpack_scratch_bytes(131072, 1)
-    assert one > 0 and L.asciichat_hip_zpack_scratch_bytes(131073, 1) > one
-    assert L.asciichat_hip_zpack_scratch_bytes(36864, 256) == 256 * L.asciichat_hip_zpack_scratch_bytes(36864, 1)
-    buf = np.zeros(4096 + 64, dtype=np.uint8)
-    a = buf.ctypes.data + (-buf.ctypes.data) % 16
-    need = L.asciichat_hip_zpack_scratch_bytes(1024, 2)
+    ZW.check_refusals(ZW.NARROW)
 
-    def call(base=a, stride=1024, ln=a, mx=1024, n=2, crc=a, hdr=a, dst=a, off=a, lo=a, scratch=a, sbytes=need):
-        return L.asciichat_hip_frame_packets_zpacked(base, stride, ln, mx, n, a, crc, hdr, a, dst, 4096, off, lo, scratch, sbytes, None)
-
-    for bad in (dict(base=None), dict(base=a + 1), dict(stride=1000), dict(ln=None), dict(mx=0), dict(mx=0xFFFFFFF0), dict(n=0),
-                dict(crc=None), dict(hdr=None), dict(dst=None), dict(dst=a + 8), dict(off=a + 4), dict(lo=a + 2), dict(scratch=None),
-                dict(scratch=a + 4), dict(sbytes=need - 1), dict(stride=512)):
-        assert call(**bad) == INVALID, bad
-    assert L.asciichat_hip_plan_render_packets_zpacked(None, a, 1024, a, a, a, a, a, a, 4096, a, a, a, need, None) == INVALID
-    if L.asciichat_hip_device_count() == 0:
-        assert call() == NO_DEVICE
 
 
 def test_frames_of_two_and_three_pieces():

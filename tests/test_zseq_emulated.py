@@ -3,9 +3,6 @@ piece size) under the CPU emulator against the restatement (tests/zseq_ref.py) a
 sent lengths, headers, checksums and packet checksums byte for byte, nothing stored outside the frames -- at the product's
 piece size and, from a second library built with ACHIP_ZSEQ_PIECE=512, over frames of many blocks; the kernels' constant
 tables; and what the product library decides before it needs a device."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
 import zhuf_ref as Z
@@ -13,6 +10,7 @@ import zpack_support as ZS
 import zseq_cases as SC
 import zseq_ref as S
 import zwide_support as WS
+import zwire as ZW
 
 CASES = SC.cases()
 CUTS = SC.cases(SC.SMALL)
@@ -104,33 +102,4 @@ def test_more_frames_than_threads_of_the_plan():
 
 
 def test_library_refuses_before_it_needs_a_device_and_needs_one_after():
-    L = C.CDLL(ZS.LIB)
-    vp, sz, u32, ci = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int
-    L.asciichat_hip_zpack_seq_scratch_bytes.restype = sz
-    L.asciichat_hip_zpack_seq_scratch_bytes.argtypes = [u32, ci]
-    L.asciichat_hip_frame_packets_zpacked_seq.restype = ci
-    L.asciichat_hip_frame_packets_zpacked_seq.argtypes = [vp, sz, vp, u32, ci, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
-    L.asciichat_hip_plan_render_packets_zpacked_seq.restype = ci
-    L.asciichat_hip_plan_render_packets_zpacked_seq.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
-    L.asciichat_hip_device_count.restype = ci
-    NO_DEVICE, INVALID = 200, 86
-    seq = L.asciichat_hip_zpack_seq_scratch_bytes
-    assert seq(0, 4) == 0 and seq(100, 0) == 0 and seq(0xFFFFFFF0, 1) == 0
-    # 64 bytes per block and 32 per frame of records, a slot of min(8192, max_len) bytes (rounded to 16) per block
-    assert seq(100, 1) == 64 + 32 + 112 and seq(8192, 1) == 64 + 32 + 8192 and seq(8193, 1) == 2 * (64 + 8192) + 32
-    assert seq(36864, 256) == 256 * seq(36864, 1) == 256 * (5 * (64 + 8192) + 32)
-    assert seq(1024, 2) == SC.emulator().emu_zseq_scratch_bytes(1024, 2) and seq(70000, 3) == SC.emulator().emu_zseq_scratch_bytes(70000, 3)
-    buf = np.zeros(8192 + 64, dtype=np.uint8)
-    a = buf.ctypes.data + (-buf.ctypes.data) % 16
-    need = seq(1024, 2)
-
-    def call(base=a, stride=1024, ln=a, mx=1024, n=2, crc=a, hdr=a, dst=a, off=a, lo=a, scratch=a, sbytes=need):
-        return L.asciichat_hip_frame_packets_zpacked_seq(base, stride, ln, mx, n, a, crc, hdr, a, dst, 4096, off, lo, scratch, sbytes, None)
-
-    for bad in (dict(base=None), dict(base=a + 1), dict(stride=1000), dict(ln=None), dict(mx=0), dict(mx=0xFFFFFFF0), dict(n=0),
-                dict(crc=None), dict(hdr=None), dict(dst=None), dict(dst=a + 8), dict(off=a + 4), dict(lo=a + 2), dict(scratch=None),
-                dict(scratch=a + 4), dict(sbytes=need - 1), dict(stride=512)):
-        assert call(**bad) == INVALID, bad
-    assert L.asciichat_hip_plan_render_packets_zpacked_seq(None, a, 1024, a, a, a, a, a, a, 4096, a, a, a, need, None) == INVALID
-    if L.asciichat_hip_device_count() == 0:
-        assert call() == NO_DEVICE
+    ZW.check_refusals(ZW.SEQ)

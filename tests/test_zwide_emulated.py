@@ -2,8 +2,6 @@
 restatement (tests/zwide_ref.py) and the oracle's CRC -- destination, offsets, sent lengths, headers, checksums and packet
 checksums byte for byte, nothing stored outside the frames, the tables and trees in the scratch records -- and what the
 product library decides before it needs a device."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -11,6 +9,7 @@ import zhuf_ref as Z
 import zpack_support as ZS
 import zwide_ref as W
 import zwide_support as WS
+import zwire as ZW
 
 CASES = WS.wide_cases()
 SMALL = 2048  # the second emulator library's ACHIP_ZPACK_PIECE
@@ -106,32 +105,4 @@ def test_capacities_that_end_inside_a_block():
 
 
 def test_library_refuses_before_it_needs_a_device_and_needs_one_after():
-    L = C.CDLL(ZS.LIB)
-    vp, sz, u32, ci = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int
-    for name in ("asciichat_hip_zpack_wide_scratch_bytes", "asciichat_hip_zpack_scratch_bytes"):
-        getattr(L, name).restype = sz
-        getattr(L, name).argtypes = [u32, ci]
-    L.asciichat_hip_frame_packets_zpacked_wide.restype = ci
-    L.asciichat_hip_frame_packets_zpacked_wide.argtypes = [vp, sz, vp, u32, ci, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
-    L.asciichat_hip_plan_render_packets_zpacked_wide.restype = ci
-    L.asciichat_hip_plan_render_packets_zpacked_wide.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
-    L.asciichat_hip_device_count.restype = ci
-    NO_DEVICE, INVALID = 200, 86
-    wide = L.asciichat_hip_zpack_wide_scratch_bytes
-    assert wide(0, 4) == 0 and wide(100, 0) == 0 and wide(0xFFFFFFF0, 1) == 0
-    assert wide(131072, 1) == 4 * (WS.REC_WORDS + 8) and wide(131073, 1) == 4 * (2 * WS.REC_WORDS + 8)
-    assert wide(36864, 256) == 256 * wide(36864, 1) > L.asciichat_hip_zpack_scratch_bytes(36864, 256)
-    buf = np.zeros(8192 + 64, dtype=np.uint8)
-    a = buf.ctypes.data + (-buf.ctypes.data) % 16
-    need = wide(1024, 2)
-
-    def call(base=a, stride=1024, ln=a, mx=1024, n=2, crc=a, hdr=a, dst=a, off=a, lo=a, scratch=a, sbytes=need):
-        return L.asciichat_hip_frame_packets_zpacked_wide(base, stride, ln, mx, n, a, crc, hdr, a, dst, 4096, off, lo, scratch, sbytes, None)
-
-    for bad in (dict(base=None), dict(base=a + 1), dict(stride=1000), dict(ln=None), dict(mx=0), dict(mx=0xFFFFFFF0), dict(n=0),
-                dict(crc=None), dict(hdr=None), dict(dst=None), dict(dst=a + 8), dict(off=a + 4), dict(lo=a + 2), dict(scratch=None),
-                dict(scratch=a + 4), dict(sbytes=need - 1), dict(sbytes=L.asciichat_hip_zpack_scratch_bytes(1024, 2)), dict(stride=512)):
-        assert call(**bad) == INVALID, bad
-    assert L.asciichat_hip_plan_render_packets_zpacked_wide(None, a, 1024, a, a, a, a, a, a, 4096, a, a, a, need, None) == INVALID
-    if L.asciichat_hip_device_count() == 0:
-        assert call() == NO_DEVICE
+    ZW.check_refusals(ZW.WIDE)

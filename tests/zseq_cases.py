@@ -1,18 +1,15 @@
 """zseq wire form test support: the boundary families the restatement, the emulated and the GPU tests share -- every case asserts
-its premise with the restatement (tests/zseq_ref.py) -- the kernels under the CPU emulator (tests/hipemu/zseq_emu_driver.cpp),
-and the check of a call's outputs against the restatement, as zwide_support.check does it for the wide form.  TESTS ONLY."""
-import ctypes as C
-import os
-import struct
-import subprocess
+its premise with the restatement (tests/zseq_ref.py) -- and tests/zwire.py's expectation, check and emulator run bound to the
+sequence form.  TESTS ONLY."""
+import functools
 
 import numpy as np
 
-import orc
 import zhuf_ref as Z
 import zpack_support as ZS
 import zseq_ref as S
 import zwide_support as WS
+import zwire as ZW
 
 FILL, ERR = ZS.FILL, ZS.ERR
 SMALL = 512  # the second emulator library's ACHIP_ZSEQ_PIECE
@@ -194,106 +191,6 @@ def cases(piece=S.PIECE):
     return out
 
 
-# ---- expectation -------------------------------------------------------------------------------------------------------
-def expect(frames, dims, piece=S.PIECE):
-    """-> per frame dict(sent, payload, hdr, crc, pkt, off), total"""
-    res, off = [], 0
-    for f, (w, h) in zip(frames, dims):
-        if isinstance(f, int):
-            res.append(dict(sent=0, len_out=f, payload=b"", hdr=bytes(24), crc=0, pkt=0, off=off, flags=0))
-            continue
-        payload, csz, flags = S.wire(f, piece)
-        crc = orc.crc32c(f)
-        hdr = Z.packet_header(w, h, len(f), csz, crc, flags)
-        res.append(dict(sent=len(payload), len_out=len(payload), payload=payload, hdr=hdr, crc=crc, pkt=orc.crc32c(hdr + payload),
-                        off=off, flags=flags))
-        off += (len(payload) + 15) // 16 * 16
-    return res, off
-
-
-def check(frames, dims, out, capacity, what="", piece=S.PIECE):
-    """offsets, sent lengths, checksums, headers as the reference's receiver checks them, packet checksums, payloads byte for
-    byte and decoded back (own decoder, libzstd where it loads), and no store outside the frames"""
-    exp, total = expect(frames, dims, piece)
-    n = len(frames)
-    assert int(out["off"][n]) == total, (what, int(out["off"][n]), total)
-    written = np.zeros(len(out["dst"]), dtype=bool)
-    for i, (f, e) in enumerate(zip(frames, exp)):
-        tag = f"{what} frame {i}"
-        assert int(out["off"][i]) == e["off"], tag
-        assert int(out["len_out"][i]) == e["len_out"], (tag, int(out["len_out"][i]), e["len_out"])
-        assert int(out["crc"][i]) == e["crc"], tag
-        hdr = out["hdr"][24 * i:24 * i + 24].tobytes()
-        assert hdr == e["hdr"], (tag, hdr.hex(), e["hdr"].hex())
-        if isinstance(f, int):
-            assert int(out["pkt"][i]) == 0, tag
-            continue
-        w_, h_, orig, csz, cks, flags = struct.unpack(">6I", hdr)
-        assert orig == len(f) and cks == orc.crc32c(f) and flags == e["flags"]
-        assert (csz == e["sent"] and flags == Z.FLAG_COMPRESSED) or (csz == 0 and flags == 0 and e["sent"] == len(f))
-        room = (e["sent"] + 15) // 16 * 16
-        if e["off"] + room <= capacity:
-            got = out["dst"][e["off"]:e["off"] + e["sent"]].tobytes()
-            assert got == e["payload"], (tag, "payload differs at", next(k for k in range(len(got)) if got[k] != e["payload"][k]))
-            if flags:
-                assert S.decode(got, piece) == f, tag
-                if Z.libzstd() is not None:
-                    assert Z.zstd_decompress(got, len(f)) == f, tag
-                written[e["off"]:e["off"] + e["sent"]] = True
-            else:
-                written[e["off"]:e["off"] + room] = True
-        assert int(out["pkt"][i]) == e["pkt"], tag
-    assert (out["dst"][~written] == FILL).all(), f"{what}: a store outside the frames ({np.flatnonzero((out['dst'] != FILL) & ~written)[:4]})"
-
-
-# ---- the emulator ------------------------------------------------------------------------------------------------------
-_emu = {}
-
-
-def emulator(piece=S.PIECE):
-    """the emulator library of the zseq kernels; another piece size gives a second library built with that ACHIP_ZSEQ_PIECE"""
-    if piece not in _emu:
-        drv = os.path.join(ZS.EMU_DIR, "zseq_emu_driver.cpp")
-        srcs = [drv, os.path.join(ZS.EMU_DIR, "hip_emu.h"), os.path.join(ZS.EMU_DIR, "gfx950_ops.hpp")] + \
-               [os.path.join(ZS.CSRC, f) for f in ("zseq_kernels.hpp", "zpack_kernels.hpp", "zpack.h", "crc_math.hpp", "render_kernels.hpp")]
-        so = os.path.join(ZS.OUT_DIR, "libzseq_emu.so" if piece == S.PIECE else "libzseq_emu_%d.so" % piece)
-        define = [] if piece == S.PIECE else ["-DACHIP_ZSEQ_PIECE=%du" % piece]
-        if not (os.path.exists(so) and all(os.path.getmtime(s) <= os.path.getmtime(so) for s in srcs)):
-            os.makedirs(ZS.OUT_DIR, exist_ok=True)
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-I" + ZS.EMU_DIR, "-I" + ZS.CSRC, "-I" + ZS.INC] + define +
-                                  [drv, "-o", tmp])
-            os.replace(tmp, so)
-        L = C.CDLL(so)
-        vp = C.c_void_p
-        L.emu_zseq_scratch_bytes.restype = C.c_size_t
-        L.emu_zseq_scratch_bytes.argtypes = [C.c_uint32, C.c_int]
-        L.emu_zseq.restype = None
-        L.emu_zseq.argtypes = [vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
-        L.emu_zseq_piece.restype = C.c_uint32
-        L.emu_zseq_tables.restype = C.POINTER(C.c_uint32)
-        assert L.emu_zseq_piece() == piece
-        _emu[piece] = L
-    return _emu[piece]
-
-
-def emu_run(frames, dims, capacity=None, tail=256, piece=S.PIECE, stride=None):
-    """the four kernels over the frames -> (out dict for check(), capacity)"""
-    L = emulator(piece)
-    n = len(frames)
-    slab0, stride, ln, mx = ZS.slab_of(frames, stride)
-    slab = ZS._aligned(len(slab0) + 16, FILL)
-    slab[:len(slab0)] = slab0
-    _, total = expect(frames, dims, piece)
-    cap = total if capacity is None else capacity
-    dst = ZS._aligned(max(cap, total) + tail, FILL)
-    off = np.full(n + 1, 0xEEEEEEEE, dtype=np.uint64)
-    len_out = np.full(n, 0xEEEEEEEE, dtype=np.uint32)
-    crc = np.full(n, 0xEEEEEEEE, dtype=np.uint32)
-    pkt = np.full(n, 0xEEEEEEEE, dtype=np.uint32)
-    hdr = ZS._aligned(24 * n, FILL)
-    d = np.array(dims, dtype=np.uint32).reshape(n, 2)
-    scratch = np.full(L.emu_zseq_scratch_bytes(mx, n) // 8 + 1, 0xEEEEEEEEEEEEEEEE, dtype=np.uint64)
-    L.emu_zseq(slab.ctypes.data, stride, ln.ctypes.data, mx, n, d.ctypes.data, crc.ctypes.data, hdr.ctypes.data, pkt.ctypes.data,
-               dst.ctypes.data, cap, off.ctypes.data, len_out.ctypes.data, scratch.ctypes.data)
-    return dict(dst=dst, off=off, len_out=len_out, crc=crc, hdr=hdr, pkt=pkt), cap
+# ---- the shared expectation, check and emulator run (tests/zwire.py), bound to the sequence form ----------------------------
+FORM = ZW.SEQ
+expect, check, emulator, emu_run = (functools.partial(f, FORM) for f in (ZW.expect, ZW.check, ZW.emulator, ZW.emu_run))
