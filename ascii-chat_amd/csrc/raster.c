@@ -185,6 +185,52 @@ int asciichat_raster_run(asciichat_raster_t *r, const uint8_t *frames_dev, size_
   return rc ? rc : asciichat_raster_draw(r, n, pixels_dev, image_pitch, stream);
 }
 
+size_t asciichat_raster_yuv420_bytes(int width_px, int height_px) {
+  if (width_px < 2 || height_px < 2 || (width_px & 1) || (height_px & 1))
+    return 0;
+  return (size_t)width_px * (size_t)height_px / 2u * 3u;
+}
+
+size_t asciichat_raster_yuv420_pitch(const asciichat_raster_t *r) {
+  return asciichat_raster_yuv420_bytes(asciichat_raster_width_px(r), asciichat_raster_height_px(r));
+}
+
+/* what both YUV entries ask of their output; nothing is launched unless it holds */
+static int yuv_ok(const asciichat_raster_t *h, int n, const uint8_t *yuv_dev, size_t image_pitch, int layout, const char *what) {
+  const int rc = frames_ok(h, n, what);
+  if (rc)
+    return rc;
+  const size_t need = asciichat_raster_yuv420_pitch(h);
+  if (!need)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: a %d x %d image has no 4:2:0 planes: both must be even", what,
+                asciichat_raster_width_px(h), asciichat_raster_height_px(h));
+  if (layout != ASCIICHAT_RASTER_YUV_I420 && layout != ASCIICHAT_RASTER_YUV_NV12)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: layout %d is neither I420 nor NV12", what, layout);
+  if (!yuv_dev || ((uintptr_t)yuv_dev & 3u) || (image_pitch & 3u))
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: 4-byte aligned planes and image pitch are required", what);
+  if (image_pitch < need)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: pitch %zu below an image's %zu bytes", what, image_pitch, need);
+  return 0;
+}
+
+int asciichat_raster_draw_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev, size_t image_pitch, int layout, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  const int rc = yuv_ok(h, n, yuv_dev, image_pitch, layout, "raster_draw_yuv420");
+  if (rc)
+    return rc;
+  return hip_check((hipError_t)raster_launch_draw_yuv(&h->p, h->cells, n, yuv_dev, (uint64_t)image_pitch, layout, stream),
+                   "raster yuv draw launch");
+}
+
+int asciichat_raster_run_yuv420(asciichat_raster_t *r, const uint8_t *frames_dev, size_t frame_stride, const uint32_t *len_dev, int n,
+                                uint8_t *yuv_dev, size_t image_pitch, int layout, uint32_t *status_dev, void *stream) {
+  int rc = yuv_ok(raster_of(r), n, yuv_dev, image_pitch, layout, "raster_run_yuv420");
+  if (rc)
+    return rc;
+  rc = asciichat_raster_parse(r, frames_dev, frame_stride, len_dev, n, status_dev, stream);
+  return rc ? rc : asciichat_raster_draw_yuv420(r, n, yuv_dev, image_pitch, layout, stream);
+}
+
 void asciichat_raster_destroy(asciichat_raster_t *r) {
   asciichat_raster_t *h = raster_of(r);
   if (!h)

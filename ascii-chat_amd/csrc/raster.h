@@ -144,11 +144,33 @@ static inline unsigned raster_draw_split(const raster_params_t *p, int n) {
   return split > tiles ? tiles : split;
 }
 
+/* ---- the YUV 4:2:0 draw (raster_yuv_kernels.hpp) ---- */
+#define RASTER_YUV_LANE_PX 4      /* pixel columns of two image rows a lane owns at a time: two 2x2 blocks, one slot */
+#define RASTER_YUV_TILE_CELLS 256 /* cell columns whose records sit in LDS at a time, with a neighbour on either side */
+
+/* cell rows a workgroup owns: its image rows pair up, so two when the cell height is odd (rows is then even, as H is) */
+static inline unsigned raster_yuv_span(const raster_params_t *p) { return (p->cell_h & 1) ? 2u : 1u; }
+static inline size_t raster_yuv_lds(const raster_params_t *p) {
+  const size_t cells = (raster_yuv_span(p) + 1u) * (RASTER_TILE_GROUPS * 4u + 8u) * 20u; /* the span's cell rows and the one below */
+  return cells + (p->atlas_in_lds ? ((size_t)p->coverage_bytes + 15u) & ~(size_t)15u : 0u);
+}
+/* workgroups a strip's slots are spread over: as raster_draw_split, small batches spread them, large ones walk them in one
+ * workgroup (the staged atlas is loaded once per workgroup) -- at most as many as the first tile's slots fill */
+static inline unsigned raster_yuv_split(const raster_params_t *p, int n) {
+  const unsigned span = raster_yuv_span(p), strips = (unsigned)n * ((unsigned)p->rows / span);
+  const unsigned ncol = p->cols < RASTER_YUV_TILE_CELLS ? (unsigned)p->cols : RASTER_YUV_TILE_CELLS;
+  const unsigned slots = (ncol * (unsigned)p->cell_w + RASTER_YUV_LANE_PX - 1u) / RASTER_YUV_LANE_PX * (span * (unsigned)p->cell_h / 2u);
+  const unsigned full = (slots + RASTER_BLOCK - 1u) / RASTER_BLOCK, split = strips >= 2048u ? 1u : 2048u / strips;
+  return split > full ? full : split;
+}
+
 /* the launchers (raster.hip); each returns a hipError_t.  starts: n * (rows + 2) words, recs: n * (rows + 1), cells:
- * n * rows * cols, all device memory of the handle. */
+ * n * rows * cols, all device memory of the handle.  draw_yuv: width and height even, layout one of ASCIICHAT_RASTER_YUV_*. */
 int raster_launch_parse(const raster_params_t *p, const uint8_t *frames, uint64_t frame_stride, const uint32_t *len, int n,
                         uint32_t *starts, raster_rowrec_t *recs, raster_cell_t *cells, uint32_t *status, void *stream);
 int raster_launch_draw(const raster_params_t *p, const raster_cell_t *cells, int n, uint8_t *pixels, uint64_t image_pitch, void *stream);
+int raster_launch_draw_yuv(const raster_params_t *p, const raster_cell_t *cells, int n, uint8_t *yuv, uint64_t image_pitch, int layout,
+                           void *stream);
 
 #ifdef __cplusplus
 }

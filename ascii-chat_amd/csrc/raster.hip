@@ -1,9 +1,10 @@
-/* raster.hip -- the launchers of the rasteriser (raster_kernels.hpp); the host side is raster.c. */
+/* raster.hip -- the launchers of the rasteriser (raster_kernels.hpp, raster_yuv_kernels.hpp); the host side is raster.c. */
 #include <hip/hip_runtime.h>
 
 #include "launch_common.hpp"
 #include "raster.h"
 #include "raster_kernels.hpp"
+#include "raster_yuv_kernels.hpp"
 
 extern "C" int raster_launch_parse(const raster_params_t *p, const uint8_t *frames, uint64_t frame_stride, const uint32_t *len, int n,
                                    uint32_t *starts, raster_rowrec_t *recs, raster_cell_t *cells, uint32_t *status, void *stream) {
@@ -38,5 +39,20 @@ extern "C" int raster_launch_draw(const raster_params_t *p, const raster_cell_t 
   const unsigned tiles = (unsigned)raster_tiles(p), strips = (unsigned)n * (unsigned)p->rows, split = raster_draw_split(p, n);
   hipLaunchKernelGGL(achip::raster::draw_kernel, dim3(strips, split), dim3(RASTER_BLOCK), (size_t)lds, static_cast<hipStream_t>(stream), *p,
                      cells, pixels, image_pitch, tiles);
+  return (int)hipGetLastError();
+}
+
+extern "C" int raster_launch_draw_yuv(const raster_params_t *p, const raster_cell_t *cells, int n, uint8_t *yuv, uint64_t image_pitch,
+                                      int layout, void *stream) {
+  if (!p || !cells || n <= 0 || !yuv || ((p->cols * p->cell_w) & 1) || ((p->rows * p->cell_h) & 1) ||
+      (layout != ASCIICHAT_RASTER_YUV_I420 && layout != ASCIICHAT_RASTER_YUV_NV12))
+    return (int)hipErrorInvalidValue;
+  const int lds = (int)raster_yuv_lds(p);
+  const hipError_t e = achip::ensure_dynamic_lds<achip::raster::draw_yuv_kernel>(lds);
+  if (e != hipSuccess)
+    return (int)e;
+  const unsigned strips = (unsigned)n * ((unsigned)p->rows / raster_yuv_span(p));
+  hipLaunchKernelGGL(achip::raster::draw_yuv_kernel, dim3(strips, raster_yuv_split(p, n)), dim3(RASTER_BLOCK), (size_t)lds,
+                     static_cast<hipStream_t>(stream), *p, cells, yuv, image_pitch, layout == ASCIICHAT_RASTER_YUV_NV12 ? 1u : 0u);
   return (int)hipGetLastError();
 }

@@ -1,15 +1,18 @@
-"""ctypes binding of libasciichat_raster.so (include/asciichat_raster.h): rendered ANSI frames to RGBA pixels on the device."""
+"""ctypes binding of libasciichat_raster.so (include/asciichat_raster.h): rendered ANSI frames to RGBA pixels, or straight to
+YUV 4:2:0 planes, on the device."""
 import ctypes as C
 import os
 
 __all__ = ["Raster", "RasterFont", "RasterGlyph", "raster_font", "raster_lib", "RASTER_LIB_PATH", "RASTER_NO_FRAME", "RASTER_BAD_UTF8",
-           "RASTER_UNKNOWN", "RASTER_OVERFLOW_COLS", "RASTER_OVERFLOW_ROWS", "RASTER_INDEXED_FLAT", "RASTER_INDEXED_XTERM"]
+           "RASTER_UNKNOWN", "RASTER_OVERFLOW_COLS", "RASTER_OVERFLOW_ROWS", "RASTER_INDEXED_FLAT", "RASTER_INDEXED_XTERM", "RASTER_YUV_I420",
+           "RASTER_YUV_NV12"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 RASTER_LIB_PATH = os.path.join(HERE, "libasciichat_raster.so")
 
 RASTER_NO_FRAME, RASTER_BAD_UTF8, RASTER_UNKNOWN, RASTER_OVERFLOW_COLS, RASTER_OVERFLOW_ROWS = 1, 2, 4, 8, 16
 RASTER_INDEXED_FLAT, RASTER_INDEXED_XTERM = 1, 2
+RASTER_YUV_I420, RASTER_YUV_NV12 = 1, 2  # Y, U, V planes | Y plane, then U V pairs
 
 
 class RasterGlyph(C.Structure):  # asciichat_raster_glyph_t
@@ -49,6 +52,10 @@ def raster_lib():
                             ("asciichat_raster_run", ci, [vp, vp, sz, vp, ci, vp, sz, vp, vp]),
                             ("asciichat_raster_parse", ci, [vp, vp, sz, vp, ci, vp, vp]),
                             ("asciichat_raster_draw", ci, [vp, ci, vp, sz, vp]),
+                            ("asciichat_raster_yuv420_bytes", sz, [ci, ci]),
+                            ("asciichat_raster_yuv420_pitch", sz, [vp]),
+                            ("asciichat_raster_run_yuv420", ci, [vp, vp, sz, vp, ci, vp, sz, ci, vp, vp]),
+                            ("asciichat_raster_draw_yuv420", ci, [vp, ci, vp, sz, ci, vp]),
                             ("asciichat_raster_destroy", None, [vp])):
         fn = getattr(L, name)
         fn.restype = res
@@ -75,7 +82,8 @@ def raster_font(cell_w, cell_h, baseline, glyphs, coverage, default_fg=0xCCCCCC,
 
 class Raster:
     """A rasteriser of cols x rows cell frames (asciichat_raster_*): run() turns the frames a Plan.render left in device memory
-    into RGBA images, one font-cell rectangle per character.  Not a parity path where DESIGN.md 7 says so."""
+    into RGBA images, one font-cell rectangle per character; run_yuv420() into YUV 4:2:0 planes for an encoder instead.  Not a
+    parity path where DESIGN.md 7 says so."""
 
     def __init__(self, font, cols, rows, max_frames):
         self.L = raster_lib()
@@ -87,6 +95,7 @@ class Raster:
         self.width = self.L.asciichat_raster_width_px(self._h)
         self.height = self.L.asciichat_raster_height_px(self._h)
         self.pitch = int(self.L.asciichat_raster_image_pitch(self._h))
+        self.yuv_pitch = int(self.L.asciichat_raster_yuv420_pitch(self._h))  # width * height * 3 / 2; 0 when either is odd
 
     def last_error(self):
         return self.L.asciichat_raster_last_error().decode("utf-8", "replace")
@@ -107,6 +116,23 @@ class Raster:
         rc = self.L.asciichat_raster_draw(self._h, n, pixels_ptr, self.pitch if image_pitch is None else image_pitch, stream)
         if rc != 0:
             raise RuntimeError(f"asciichat_raster_draw failed ({rc}): {self.last_error()}")
+
+    def run_yuv420(self, frames_ptr, frame_stride, len_ptr, n, yuv_ptr, status_ptr, layout, image_pitch=None, stream=0):
+        """run(), but image i is the YUV 4:2:0 planes (layout RASTER_YUV_I420 | RASTER_YUV_NV12) at yuv_ptr + i * image_pitch, a
+        multiple of 4 and at least yuv_pitch (default: yuv_pitch rounded up to 4); width and height must be even"""
+        rc = self.L.asciichat_raster_run_yuv420(self._h, frames_ptr, frame_stride, len_ptr, n, yuv_ptr, self._yuv_pitch(image_pitch),
+                                                layout, status_ptr, stream)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_raster_run_yuv420 failed ({rc}): {self.last_error()}")
+
+    def draw_yuv420(self, n, yuv_ptr, layout, image_pitch=None, stream=0):
+        """the cells the last parse() left, as run_yuv420() draws them"""
+        rc = self.L.asciichat_raster_draw_yuv420(self._h, n, yuv_ptr, self._yuv_pitch(image_pitch), layout, stream)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_raster_draw_yuv420 failed ({rc}): {self.last_error()}")
+
+    def _yuv_pitch(self, image_pitch):
+        return (self.yuv_pitch + 3) // 4 * 4 if image_pitch is None else image_pitch
 
     def close(self):
         if self._h:

@@ -1,9 +1,10 @@
 /*
- * asciichat_raster.h -- libasciichat_raster.so: rendered ANSI frames rasterised to RGBA pixels on the device, one font-cell
- * rectangle per character, with a caller-supplied glyph atlas.  The step the reference takes in term_renderer_feed
- * (lib/media/render/terminal.c:405-529, blit_glyph :170-193) before it encodes video.  An opt-in batch pass and NOT a parity
- * path where DESIGN.md 7 says so: every frame starts from a default pen on a blank screen, nothing wraps or scrolls, every
- * codepoint takes one column, and only the grammar below is interpreted.
+ * asciichat_raster.h -- libasciichat_raster.so: rendered ANSI frames rasterised to RGBA pixels -- or straight to YUV 4:2:0
+ * planes, at the end of this file -- on the device, one font-cell rectangle per character, with a caller-supplied glyph
+ * atlas.  The step the reference takes in term_renderer_feed (lib/media/render/terminal.c:405-529, blit_glyph :170-193)
+ * before it encodes video.  An opt-in batch pass and NOT a parity path where DESIGN.md 7 says so: every frame starts from a
+ * default pen on a blank screen, nothing wraps or scrolls, every codepoint takes one column, and only the grammar below is
+ * interpreted.
  *
  * A library of its own: it needs nothing of libasciichat_hip.so and shares only achip_types.h (ACHIP_LEN_OVERFLOW) and the
  * values of the error codes with it.
@@ -109,6 +110,33 @@ int asciichat_raster_run(asciichat_raster_t *r, const uint8_t *frames_dev, size_
 int asciichat_raster_parse(asciichat_raster_t *r, const uint8_t *frames_dev, size_t frame_stride, const uint32_t *len_dev, int n,
                            uint32_t *status_dev, void *stream);
 int asciichat_raster_draw(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, void *stream);
+
+/* ---- straight to YUV 4:2:0 planes, for an encoder -------------------------------------------------------------------------
+ * The same frames, the same parse and the same compositing, but what is stored is the composited pixel's R, G, B (alpha plays
+ * no part) converted by the integer arithmetic of the reference's h265_encoder_ascii_to_yuv420 (lib/video/h265/encoder.c:
+ * 247-289), byte for byte:
+ *   Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16                         per pixel                               (:264)
+ *   r, g, b = (p00 + p10 + p01 + p11) / 4, truncating                   per 2x2 block and channel               (:276-278)
+ *   U = ((-38 r - 74 g + 112 b + 128) >> 8) + 128,  V = ((112 r - 94 g - 18 b + 128) >> 8) + 128    (arithmetic shift; :281, :285)
+ * (Y is within 16..235 and U, V within 16..240 for every input, so the reference's clamp never acts.)  No RGBA image is
+ * written on the way: 1.5 bytes per pixel instead of 4.
+ *   I420: Y[W * H], then U[(W/2) * (H/2)], then V[(W/2) * (H/2)], rows tight (W, W/2, W/2) -- encoder.c:248-250, 314-319
+ *   NV12: Y[W * H], then (W/2) * (H/2) pairs U, V, rows of W bytes -- what hardware encoders take
+ * W = cols * cell_w and H = rows * cell_h must both be even: the reference's loop reads past an odd image and leaves its
+ * planes short, which is not reproduced -- the YUV entries refuse such a handle (ERR_INVALID_PARAM, nothing launched). */
+#define ASCIICHAT_RASTER_YUV_I420 1
+#define ASCIICHAT_RASTER_YUV_NV12 2
+
+size_t asciichat_raster_yuv420_bytes(int width_px, int height_px); /* W * H * 3 / 2; 0 when either is < 2 or odd.  Needs no device */
+size_t asciichat_raster_yuv420_pitch(const asciichat_raster_t *r); /* that, of the handle; 0 for NULL or an odd size */
+/* As run() and draw(): image i goes to yuv_dev + i * image_pitch (multiples of 4 both, image_pitch >= yuv420_pitch), in
+ * `layout`; nothing outside the W * H * 3 / 2 bytes of an image is written; a NO_FRAME frame is the blank image's conversion;
+ * status_dev is what run() reports for the same frames.  1 <= n <= max_frames.  Asynchronous on `stream`: never synchronises,
+ * allocates nothing.  draw_yuv420 draws the cells the last parse() left. */
+int asciichat_raster_run_yuv420(asciichat_raster_t *r, const uint8_t *frames_dev, size_t frame_stride, const uint32_t *len_dev, int n,
+                                uint8_t *yuv_dev, size_t image_pitch, int layout, uint32_t *status_dev, void *stream);
+int asciichat_raster_draw_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev, size_t image_pitch, int layout, void *stream);
+
 void asciichat_raster_destroy(asciichat_raster_t *r);
 
 #ifdef __cplusplus
