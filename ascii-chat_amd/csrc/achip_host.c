@@ -1,5 +1,6 @@
 /* achip_host.c -- see achip_host.h.  Plain C11, no GPU calls. */
 #include "achip_host.h"
+#include "achip_desc.h"
 #include "internal.h"
 #include "render_variants.h"
 
@@ -45,49 +46,8 @@ void aspect_ratio(const ssize_t img_w, const ssize_t img_h, const ssize_t width,
     *out_height = 1;
 }
 
-static int utf8_seq_len(unsigned char c) {
-  if ((c & 0xE0) == 0xC0)
-    return 2;
-  if ((c & 0xF0) == 0xE0)
-    return 3;
-  if ((c & 0xF8) == 0xF0)
-    return 4;
-  return 1;
-}
-
-int achip_lut_build(const char *palette_chars, achip_lut_t *lut) {
-  if (!palette_chars || !lut || palette_chars[0] == '\0')
-    return -1;
-  memset(lut, 0, sizeof(*lut));
-  uint32_t packed[256];
-  int count = 0;
-  size_t len = strlen(palette_chars), pos = 0;
-  while (pos < len && count < 255) {
-    int n = utf8_seq_len((unsigned char)palette_chars[pos]);
-    uint32_t g = 0;
-    for (int k = 0; k < n && pos + (size_t)k < len; k++)
-      g |= (uint32_t)(unsigned char)palette_chars[pos + (size_t)k] << (8 * k);
-    packed[count++] = g;
-    pos += (size_t)n;
-  }
-  for (int i = 0; i < 256; i++) {
-    int ci = count > 1 ? (i * (count - 1) + 127) / 255 : 0;
-    if (ci >= count)
-      ci = count - 1;
-    lut->glyph[i] = packed[ci];
-  }
-  for (int i = 0; i < 64; i++) {
-    int ci = count > 1 ? (i * (count - 1) + 31) / 63 : 0;
-    if (ci >= count)
-      ci = count - 1;
-    lut->ramp[i] = (uint8_t)ci;
-    lut->glyph64[i] = packed[ci];
-  }
-  for (int i = 0; i < 256; i++) /* the kernels take a one-byte-per-glyph fast path when nothing is multi-byte */
-    if ((lut->glyph[i] & 0xFFu) >= 128u || (lut->glyph64[i & 63] & 0xFFu) >= 128u)
-      lut->flags |= ACHIP_LUT_MULTIBYTE;
-  return 0;
-}
+/* the palette's glyph tables: one text for both libraries (achip_desc.h) */
+int achip_lut_build(const char *palette_chars, achip_lut_t *lut) { return achip_desc_lut_build(palette_chars, lut); }
 
 int achip_mode_from_caps(int color_level, int render_mode) {
   if (render_mode == 2) { /* RENDER_MODE_HALF_BLOCK */
@@ -513,26 +473,9 @@ bool achip_palette_ascii_only(const char *palette_chars) {
   return true;
 }
 
-/* The kernels address a source with 32-bit byte offsets (a frame is at most tens of MB): a descriptor whose last pixel
- * lies 4 GiB or more behind its first -- only possible with an absurd explicit row stride -- is refused on the host. */
-bool achip_frame_extent_ok(const achip_frame_t *f) {
-  if (!f || f->comp)
-    return true; /* composites carry their own (tile-sized) sources */
-  const uint64_t stride = f->src_stride > 0 ? (uint64_t)f->src_stride : 3ull * (uint64_t)(f->src_w > 0 ? f->src_w : 0);
-  if (f->src_stride < 0)
-    return false;
-  const uint64_t extent = (uint64_t)(f->src_h > 0 ? f->src_h - 1 : 0) * stride + 3ull * (uint64_t)(f->src_w > 0 ? f->src_w : 0);
-  return extent < 0xFFFFFFF0ull && stride < (1ull << 24);
-}
-
-/* The kernels compute a sample's column as (x * x_ratio) >> 16 in 32 bits (the reference's own arithmetic, image.c:315):
- * a descriptor whose last column or row would wrap that product is refused on the host, so that every kernel form samples
- * exactly what the rule in achip_types.h says.  Descriptors of sources of at most 10 000 pixels never come near it. */
-bool achip_frame_ratios_ok(const achip_frame_t *f) {
-  if (!f || f->out_w <= 0 || f->out_h <= 0)
-    return false;
-  return (uint64_t)(f->out_w - 1) * f->x_ratio < (1ull << 32) && (uint64_t)(f->out_h - 1) * f->y_ratio < (1ull << 32);
-}
+/* the two descriptor checks of every plan: their text is achip_desc.h's, shared with the rasteriser's library */
+bool achip_frame_extent_ok(const achip_frame_t *f) { return achip_desc_extent_ok(f); }
+bool achip_frame_ratios_ok(const achip_frame_t *f) { return achip_desc_ratios_ok(f); }
 
 /* cells ((pad_left + out_w) * out_h) of the largest frame: what ACHIP_UNIFORM_MAX_CELLS carries to the stream kernel */
 long achip_max_cells(const achip_frame_t *frames, int n_frames) {

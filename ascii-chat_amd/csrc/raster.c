@@ -2,7 +2,9 @@
  * raster.c -- the host side of libasciichat_raster.so (include/asciichat_raster.h): a handle checks its font and grid before
  * it needs a device (raster.h), uploads the atlas and the lookup tables once and owns every byte of scratch a run uses --
  * cells, row starts and row records for max_frames frames --, so that run() only launches (raster.hip) on the caller's
- * stream.  Nothing here comes from libasciichat_hip.so.
+ * stream.  The cells may also come straight from frame descriptors (images_set and the entries behind it, raster_images.h): a
+ * set is checked on the host and staged through one pinned block of the handle's.  Nothing here comes from
+ * libasciichat_hip.so.
  */
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
@@ -14,6 +16,7 @@
 
 #include "asciichat_raster.h"
 #include "raster.h"
+#include "raster_images.h"
 
 #define RASTER_MAGIC 0x5241535445523031ull
 
@@ -25,6 +28,12 @@ struct asciichat_raster {
   uint32_t *starts;
   raster_rowrec_t *recs;
   raster_cell_t *cells;
+  /* cells from images (raster_images.h): the atlas' codepoints for the slot table, the last set and where it is staged */
+  uint32_t *codepoints_host;
+  uint8_t *img_dev, *img_pinned; /* one block each: the table, then max_frames descriptors; allocated by the first images_set */
+  raster_img_args_t img;
+  int img_n;          /* frames of the last set, 0 before any */
+  int img_dma_queued; /* the pinned block may still be read by the copy of the last set */
 };
 
 static _Thread_local char g_error[256];
@@ -59,6 +68,10 @@ static void raster_free(asciichat_raster_t *h) {
   (void)hipFree(h->recs);
   (void)hipFree(h->starts);
   (void)hipFree(h->tables);
+  (void)hipFree(h->img_dev);
+  if (h->img_pinned)
+    (void)hipHostFree(h->img_pinned);
+  free(h->codepoints_host);
   h->magic = 0;
   free(h);
 }
@@ -80,12 +93,16 @@ int asciichat_raster_create(asciichat_raster_t **r, const asciichat_raster_font_
   const size_t at_glyphs = round16(4u * ng), at_lut = at_glyphs + sizeof(raster_glyph_t) * ng, at_cov = at_lut + 4u * 512u;
   const size_t bytes = at_cov + round16(font->coverage_bytes) + 16u;
   uint8_t *host = (uint8_t *)calloc(1, bytes);
-  if (!h || !host) {
+  uint32_t *cps = (uint32_t *)calloc(ng + 1u, sizeof(uint32_t));
+  if (!h || !host || !cps) {
     free(h);
     free(host);
+    free(cps);
     return fail(ASCIICHAT_RASTER_ERR_MEMORY, "raster_create: out of memory");
   }
   raster_tables(font, (uint32_t *)host, (raster_glyph_t *)(host + at_glyphs), (uint32_t *)(host + at_lut));
+  memcpy(cps, host, 4u * ng);
+  h->codepoints_host = cps;
   if (font->coverage_bytes)
     memcpy(host + at_cov, font->coverage, font->coverage_bytes);
   h->magic = RASTER_MAGIC;
@@ -228,6 +245,103 @@ int asciichat_raster_run_yuv420(asciichat_raster_t *r, const uint8_t *frames_dev
   if (rc)
     return rc;
   rc = asciichat_raster_parse(r, frames_dev, frame_stride, len_dev, n, status_dev, stream);
+  return rc ? rc : asciichat_raster_draw_yuv420(r, n, yuv_dev, image_pitch, layout, stream);
+}
+
+/* ---- cells straight from frame descriptors (raster_images.h) ---- */
+
+int asciichat_raster_images_set(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames, int n,
+                                void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  if (!h)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set: not a rasteriser");
+  int bad = -1;
+  const char *why = raster_images_check(mode, palette_chars, frames, n, h->max_frames, &bad);
+  if (why)
+    return bad >= 0 ? fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set: frame %d: %s", bad, why)
+                    : fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set: %s", why);
+  int rc = 0;
+  if (!h->img_dev) { /* the first set of this handle: both blocks, sized by max_frames; later sets allocate nothing */
+    const size_t bytes = raster_images_bytes(h->max_frames);
+    uint8_t *dev = NULL, *pinned = NULL;
+    rc = hip_check(hipMalloc((void **)&dev, bytes), "hipMalloc(raster images)");
+    if (!rc)
+      rc = hip_check(hipHostMalloc((void **)&pinned, bytes, hipHostMallocDefault), "hipHostMalloc(raster images)");
+    if (rc) {
+      (void)hipFree(dev);
+      return rc;
+    }
+    h->img_dev = dev;
+    h->img_pinned = pinned;
+  }
+  /* the pinned block may still be in flight from the set before, on this stream (a handle's calls are ordered on one):
+   * wait before it is overwritten, and before anything of the handle changes */
+  if (h->img_dma_queued)
+    rc = hip_check(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+  if (rc)
+    return rc;
+  h->img_dma_queued = 0;
+  raster_img_tables_t *t = (raster_img_tables_t *)h->img_pinned;
+  const uint32_t mixed = raster_images_tables(mode, palette_chars, h->codepoints_host, h->p.n_glyphs, h->p.matrix_map, t);
+  memcpy(h->img_pinned + raster_images_at_frames(), frames, (size_t)n * sizeof(achip_frame_t));
+  h->img_n = 0; /* (should the copy fail, nothing is set) */
+  rc = hip_check(hipMemcpyAsync(h->img_dev, h->img_pinned, raster_images_bytes(n), hipMemcpyHostToDevice, (hipStream_t)stream),
+                 "hipMemcpyAsync(raster images)");
+  if (rc)
+    return rc;
+  h->img_dma_queued = 1;
+  h->img.mode = mode;
+  h->img.mixed = mixed;
+  h->img.tables = (const raster_img_tables_t *)h->img_dev;
+  h->img.frames = (const achip_frame_t *)(h->img_dev + raster_images_at_frames());
+  h->img_n = n;
+  return 0;
+}
+
+/* what cells_from_images asks of its arguments; nothing is launched unless it holds */
+static int images_ok(const asciichat_raster_t *h, int n, const uint32_t *status_dev, const char *what) {
+  if (!h)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: not a rasteriser", what);
+  if (h->img_n < 1)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: no images are set (asciichat_raster_images_set)", what);
+  if (n < 1 || n > h->img_n)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: %d frames of the %d that are set", what, n, h->img_n);
+  if (!status_dev)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: a status array is required", what);
+  return 0;
+}
+
+int asciichat_raster_cells_from_images(asciichat_raster_t *r, int n, uint32_t *status_dev, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  const int rc = images_ok(h, n, status_dev, "raster_cells_from_images");
+  if (rc)
+    return rc;
+  return hip_check((hipError_t)raster_launch_cells_images(&h->p, &h->img, n, h->cells, status_dev, stream), "raster images launch");
+}
+
+int asciichat_raster_run_images(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, uint32_t *status_dev,
+                                void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  int rc = images_ok(h, n, status_dev, "raster_run_images");
+  if (rc)
+    return rc;
+  /* nothing is launched unless both stages take their arguments */
+  if (!pixels_dev || ((uintptr_t)pixels_dev & 3u) || (image_pitch & 3u) || image_pitch < asciichat_raster_image_pitch(h))
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_run_images: 4-byte aligned pixels and an image pitch of at least %zu are required",
+                asciichat_raster_image_pitch(h));
+  rc = asciichat_raster_cells_from_images(r, n, status_dev, stream);
+  return rc ? rc : asciichat_raster_draw(r, n, pixels_dev, image_pitch, stream);
+}
+
+int asciichat_raster_run_images_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev, size_t image_pitch, int layout,
+                                       uint32_t *status_dev, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  int rc = images_ok(h, n, status_dev, "raster_run_images_yuv420");
+  if (!rc)
+    rc = yuv_ok(h, n, yuv_dev, image_pitch, layout, "raster_run_images_yuv420");
+  if (rc)
+    return rc;
+  rc = asciichat_raster_cells_from_images(r, n, status_dev, stream);
   return rc ? rc : asciichat_raster_draw_yuv420(r, n, yuv_dev, image_pitch, layout, stream);
 }
 

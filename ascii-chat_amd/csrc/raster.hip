@@ -1,8 +1,10 @@
-/* raster.hip -- the launchers of the rasteriser (raster_kernels.hpp, raster_yuv_kernels.hpp); the host side is raster.c. */
+/* raster.hip -- the launchers of the rasteriser (raster_kernels.hpp, raster_yuv_kernels.hpp, raster_images_kernels.hpp); the host
+ * side is raster.c. */
 #include <hip/hip_runtime.h>
 
 #include "launch_common.hpp"
 #include "raster.h"
+#include "raster_images_kernels.hpp"
 #include "raster_kernels.hpp"
 #include "raster_yuv_kernels.hpp"
 
@@ -54,5 +56,32 @@ extern "C" int raster_launch_draw_yuv(const raster_params_t *p, const raster_cel
   const unsigned strips = (unsigned)n * ((unsigned)p->rows / raster_yuv_span(p));
   hipLaunchKernelGGL(achip::raster::draw_yuv_kernel, dim3(strips, raster_yuv_split(p, n)), dim3(RASTER_BLOCK), (size_t)lds,
                      static_cast<hipStream_t>(stream), *p, cells, yuv, image_pitch, layout == ASCIICHAT_RASTER_YUV_NV12 ? 1u : 0u);
+  return (int)hipGetLastError();
+}
+
+template <int MODE>
+static void launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int n, raster_cell_t *cells, uint32_t *status,
+                                hipStream_t s) {
+  const unsigned groups = ((unsigned)p->rows * (unsigned)p->cols + RASTER_IMG_CELLS - 1u) / RASTER_IMG_CELLS;
+  hipLaunchKernelGGL(achip::raster::cells_images_kernel<MODE>, dim3(groups, (unsigned)n), dim3(RASTER_BLOCK), 0, s, *p, *a, cells, status);
+}
+
+extern "C" int raster_launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int n, raster_cell_t *cells,
+                                          uint32_t *status, void *stream) {
+  if (!p || !a || !a->tables || !a->frames || n <= 0 || !cells || !status)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (a->mode) { /* a missing instantiation is an error, never another mode's kernel */
+  case ACHIP_MODE_MONO: launch_cells_images<ACHIP_MODE_MONO>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_TRUE_FG: launch_cells_images<ACHIP_MODE_TRUE_FG>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_256_FG: launch_cells_images<ACHIP_MODE_256_FG>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_16_FG: launch_cells_images<ACHIP_MODE_16_FG>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_TRUE_BG: launch_cells_images<ACHIP_MODE_TRUE_BG>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_HB_TRUE: launch_cells_images<ACHIP_MODE_HB_TRUE>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_HB_256: launch_cells_images<ACHIP_MODE_HB_256>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_HB_16: launch_cells_images<ACHIP_MODE_HB_16>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_HB_MONO: launch_cells_images<ACHIP_MODE_HB_MONO>(p, a, n, cells, status, s); break;
+  default: return (int)hipErrorInvalidValue;
+  }
   return (int)hipGetLastError();
 }

@@ -1,5 +1,5 @@
-"""ctypes binding of libasciichat_raster.so (include/asciichat_raster.h): rendered ANSI frames to RGBA pixels, or straight to
-YUV 4:2:0 planes, on the device."""
+"""ctypes binding of libasciichat_raster.so (include/asciichat_raster.h): rendered ANSI frames -- or the source images behind
+them, without the text -- to RGBA pixels, or straight to YUV 4:2:0 planes, on the device."""
 import ctypes as C
 import os
 
@@ -56,6 +56,10 @@ def raster_lib():
                             ("asciichat_raster_yuv420_pitch", sz, [vp]),
                             ("asciichat_raster_run_yuv420", ci, [vp, vp, sz, vp, ci, vp, sz, ci, vp, vp]),
                             ("asciichat_raster_draw_yuv420", ci, [vp, ci, vp, sz, ci, vp]),
+                            ("asciichat_raster_images_set", ci, [vp, ci, C.c_char_p, vp, ci, vp]),
+                            ("asciichat_raster_cells_from_images", ci, [vp, ci, vp, vp]),
+                            ("asciichat_raster_run_images", ci, [vp, ci, vp, sz, vp, vp]),
+                            ("asciichat_raster_run_images_yuv420", ci, [vp, ci, vp, sz, ci, vp, vp]),
                             ("asciichat_raster_destroy", None, [vp])):
         fn = getattr(L, name)
         fn.restype = res
@@ -130,6 +134,37 @@ class Raster:
         rc = self.L.asciichat_raster_draw_yuv420(self._h, n, yuv_ptr, self._yuv_pitch(image_pitch), layout, stream)
         if rc != 0:
             raise RuntimeError(f"asciichat_raster_draw_yuv420 failed ({rc}): {self.last_error()}")
+
+    def set_images(self, mode, palette, frames, stream=0):
+        """the frames the *_images methods work on: mode MODE_* 0..8, the renderers' palette, a list (or ctypes array) of
+        binding.Frame with device-visible sources; checked on the host, copied asynchronously on `stream` (the handle's one
+        stream).  No composites, no dithered mode: those stay on the text path"""
+        from .binding import Frame
+        arr = frames if isinstance(frames, C.Array) else (Frame * max(1, len(frames)))(*frames)
+        p = palette.encode("utf-8") if isinstance(palette, str) else palette
+        rc = self.L.asciichat_raster_images_set(self._h, mode, p, C.cast(arr, C.c_void_p), len(frames), stream)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_raster_images_set failed ({rc}): {self.last_error()}")
+
+    def cells_from_images(self, n, status_ptr, stream=0):
+        """parse()'s counterpart: the cells of frames 0..n-1 of the last set_images, straight from their pixels"""
+        rc = self.L.asciichat_raster_cells_from_images(self._h, n, status_ptr, stream)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_raster_cells_from_images failed ({rc}): {self.last_error()}")
+
+    def run_images(self, n, pixels_ptr, status_ptr, image_pitch=None, stream=0):
+        """cells_from_images + draw: image i at pixels_ptr + i * image_pitch, what run() gives for Plan.render's text of the same
+        descriptors; asynchronous"""
+        rc = self.L.asciichat_raster_run_images(self._h, n, pixels_ptr, self.pitch if image_pitch is None else image_pitch, status_ptr,
+                                                stream)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_raster_run_images failed ({rc}): {self.last_error()}")
+
+    def run_images_yuv420(self, n, yuv_ptr, status_ptr, layout, image_pitch=None, stream=0):
+        """cells_from_images + draw_yuv420, with run_yuv420()'s output arguments"""
+        rc = self.L.asciichat_raster_run_images_yuv420(self._h, n, yuv_ptr, self._yuv_pitch(image_pitch), layout, status_ptr, stream)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_raster_run_images_yuv420 failed ({rc}): {self.last_error()}")
 
     def _yuv_pitch(self, image_pitch):
         return (self.yuv_pitch + 3) // 4 * 4 if image_pitch is None else image_pitch

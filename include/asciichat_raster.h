@@ -137,6 +137,42 @@ int asciichat_raster_run_yuv420(asciichat_raster_t *r, const uint8_t *frames_dev
                                 uint8_t *yuv_dev, size_t image_pitch, int layout, uint32_t *status_dev, void *stream);
 int asciichat_raster_draw_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev, size_t image_pitch, int layout, void *stream);
 
+/* ---- straight from the source images, without the text --------------------------------------------------------------------
+ * For frames this project's own renderers would write (asciichat_hip_plan_render of the same descriptors, asciichat_hip.h)
+ * the text is a detour: what parse() recovers from it -- a glyph, a foreground and a background per cell -- is a function of
+ * the pixels the descriptor samples.  These entries fill the handle's cell grids from the descriptors themselves, by the
+ * renderers' own sampling, luminance, palette and colour rules; draw() and draw_yuv420() take the cells from there.  Images
+ * and status are byte for byte those of plan_render followed by run() / run_yuv420() for the same descriptors, mode and
+ * palette.  The cell grids are the handle's, shared with parse(): a draw shows the cells of whichever stage ran last.
+ *
+ * images_set is the set-up call: mode is ACHIP_MODE_* 0..8 (achip_types.h), palette_chars the renderers' palette, frames a
+ * HOST array of n descriptors (1 <= n <= max_frames) whose src are device-visible.  Everything is checked on the host before
+ * anything is copied or launched; ERR_INVALID_PARAM, with the handle's earlier set still in place, for
+ *   - a mode outside 0..8: ACHIP_MODE_16_DITHER_BG is serial error diffusion and stays on the text path;
+ *   - a NULL or empty palette, one that is not well-formed UTF-8, or one with a C0 byte or DEL (the grammar reads those as
+ *     controls, not as cells);
+ *   - n outside 1..max_frames; a descriptor with comp != NULL (composites stay on the text path) or src == NULL; a size below
+ *     1 or a negative padding; (out_w - 1) * x_ratio or (out_h - 1) * y_ratio at 2^32 or above; a source spanning 4 GiB or
+ *     more; ops with a dither bit, or with both ACHIP_OP_TINT and ACHIP_OP_FG_OVERRIDE.
+ * The descriptors and the mode's glyph table go to the device through a pinned copy the handle owns, asynchronously on
+ * `stream`: the caller's array may be freed on return.  The first set of a handle allocates (sized by max_frames), later
+ * sets allocate nothing; a set waits on `stream` first when the copy of the set before it may still be in flight.  All calls
+ * on one handle must be ordered on ONE stream, sets included, as a plan's are.
+ *
+ * cells_from_images is the new stage alone, as parse() is: frames 0..n-1 of the last set (1 <= n <= the number set) become
+ * cells, status_dev[i] their flags -- only OVERFLOW_COLS (pad_left + out_w beyond cols, in a text row of the grid) and
+ * OVERFLOW_ROWS (pad_top + text rows beyond rows) can occur; cells beyond the grid are dropped.  run_images is
+ * cells_from_images + draw, run_images_yuv420 is cells_from_images + draw_yuv420; they take and check the output arguments of
+ * run() and run_yuv420(), and launch nothing unless every stage takes its arguments.  ERR_INVALID_PARAM before any
+ * images_set.  Asynchronous on `stream`: never synchronise, allocate nothing. */
+int asciichat_raster_images_set(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames, int n,
+                                void *stream);
+int asciichat_raster_cells_from_images(asciichat_raster_t *r, int n, uint32_t *status_dev, void *stream);
+int asciichat_raster_run_images(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, uint32_t *status_dev,
+                                void *stream);
+int asciichat_raster_run_images_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev, size_t image_pitch, int layout,
+                                       uint32_t *status_dev, void *stream);
+
 void asciichat_raster_destroy(asciichat_raster_t *r);
 
 #ifdef __cplusplus
