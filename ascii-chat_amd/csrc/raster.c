@@ -33,6 +33,7 @@ struct asciichat_raster {
   uint8_t *img_dev, *img_pinned; /* one block each: the table, then max_frames descriptors; allocated by the first images_set */
   raster_img_args_t img;
   int img_n;          /* frames of the last set, 0 before any */
+  int img_comp;       /* some frame of the last set carries a composite: the kernel form with the staged sampler */
   int img_dma_queued; /* the pinned block may still be read by the copy of the last set */
 };
 
@@ -250,16 +251,9 @@ int asciichat_raster_run_yuv420(asciichat_raster_t *r, const uint8_t *frames_dev
 
 /* ---- cells straight from frame descriptors (raster_images.h) ---- */
 
-int asciichat_raster_images_set(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames, int n,
-                                void *stream) {
-  asciichat_raster_t *h = raster_of(r);
-  if (!h)
-    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set: not a rasteriser");
-  int bad = -1;
-  const char *why = raster_images_check(mode, palette_chars, frames, n, h->max_frames, &bad);
-  if (why)
-    return bad >= 0 ? fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set: frame %d: %s", bad, why)
-                    : fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set: %s", why);
+/* a checked set (composites: how many of its frames carry comp) becomes the handle's */
+static int images_stage(asciichat_raster_t *h, int mode, const char *palette_chars, const achip_frame_t *frames, int n, int composites,
+                        void *stream) {
   int rc = 0;
   if (!h->img_dev) { /* the first set of this handle: both blocks, sized by max_frames; later sets allocate nothing */
     const size_t bytes = raster_images_bytes(h->max_frames);
@@ -294,8 +288,35 @@ int asciichat_raster_images_set(asciichat_raster_t *r, int mode, const char *pal
   h->img.mixed = mixed;
   h->img.tables = (const raster_img_tables_t *)h->img_dev;
   h->img.frames = (const achip_frame_t *)(h->img_dev + raster_images_at_frames());
+  h->img_comp = composites > 0;
   h->img_n = n;
   return 0;
+}
+
+static int images_refused(const char *what, int bad, const char *why) {
+  return bad >= 0 ? fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: frame %d: %s", what, bad, why)
+                  : fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "%s: %s", what, why);
+}
+
+int asciichat_raster_images_set(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames, int n,
+                                void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  if (!h)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set: not a rasteriser");
+  int bad = -1;
+  const char *why = raster_images_check(mode, palette_chars, frames, n, h->max_frames, &bad);
+  return why ? images_refused("raster_images_set", bad, why) : images_stage(h, mode, palette_chars, frames, n, 0, stream);
+}
+
+int asciichat_raster_images_set_composites(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames,
+                                           int n, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  if (!h)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set_composites: not a rasteriser");
+  int bad = -1, composites = 0;
+  const char *why = raster_images_composites_check(mode, palette_chars, frames, n, h->max_frames, &bad, &composites);
+  return why ? images_refused("raster_images_set_composites", bad, why)
+             : images_stage(h, mode, palette_chars, frames, n, composites, stream);
 }
 
 /* what cells_from_images asks of its arguments; nothing is launched unless it holds */
@@ -316,7 +337,7 @@ int asciichat_raster_cells_from_images(asciichat_raster_t *r, int n, uint32_t *s
   const int rc = images_ok(h, n, status_dev, "raster_cells_from_images");
   if (rc)
     return rc;
-  return hip_check((hipError_t)raster_launch_cells_images(&h->p, &h->img, n, h->cells, status_dev, stream), "raster images launch");
+  return hip_check((hipError_t)raster_launch_cells_images(&h->p, &h->img, h->img_comp, n, h->cells, status_dev, stream), "raster images launch");
 }
 
 int asciichat_raster_run_images(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, uint32_t *status_dev,

@@ -60,27 +60,33 @@ extern "C" int raster_launch_draw_yuv(const raster_params_t *p, const raster_cel
 }
 
 template <int MODE>
-static void launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int n, raster_cell_t *cells, uint32_t *status,
-                                hipStream_t s) {
+static void launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, bool composites, int n, raster_cell_t *cells,
+                                uint32_t *status, hipStream_t s) {
   const unsigned groups = ((unsigned)p->rows * (unsigned)p->cols + RASTER_IMG_CELLS - 1u) / RASTER_IMG_CELLS;
-  hipLaunchKernelGGL(achip::raster::cells_images_kernel<MODE>, dim3(groups, (unsigned)n), dim3(RASTER_BLOCK), 0, s, *p, *a, cells, status);
+  if (composites) /* the staged composite descriptor is this form's only LDS */
+    hipLaunchKernelGGL((achip::raster::cells_images_kernel<MODE, true>), dim3(groups, (unsigned)n), dim3(RASTER_BLOCK), ACHIP_COMP_LDS_BYTES, s,
+                       *p, *a, cells, status);
+  else
+    hipLaunchKernelGGL((achip::raster::cells_images_kernel<MODE, false>), dim3(groups, (unsigned)n), dim3(RASTER_BLOCK), 0, s, *p, *a, cells,
+                       status);
 }
 
-extern "C" int raster_launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int n, raster_cell_t *cells,
+extern "C" int raster_launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int composites, int n, raster_cell_t *cells,
                                           uint32_t *status, void *stream) {
   if (!p || !a || !a->tables || !a->frames || n <= 0 || !cells || !status)
     return (int)hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool c = composites != 0;
   switch (a->mode) { /* a missing instantiation is an error, never another mode's kernel */
-  case ACHIP_MODE_MONO: launch_cells_images<ACHIP_MODE_MONO>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_TRUE_FG: launch_cells_images<ACHIP_MODE_TRUE_FG>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_256_FG: launch_cells_images<ACHIP_MODE_256_FG>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_16_FG: launch_cells_images<ACHIP_MODE_16_FG>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_TRUE_BG: launch_cells_images<ACHIP_MODE_TRUE_BG>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_HB_TRUE: launch_cells_images<ACHIP_MODE_HB_TRUE>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_HB_256: launch_cells_images<ACHIP_MODE_HB_256>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_HB_16: launch_cells_images<ACHIP_MODE_HB_16>(p, a, n, cells, status, s); break;
-  case ACHIP_MODE_HB_MONO: launch_cells_images<ACHIP_MODE_HB_MONO>(p, a, n, cells, status, s); break;
+  case ACHIP_MODE_MONO: launch_cells_images<ACHIP_MODE_MONO>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_TRUE_FG: launch_cells_images<ACHIP_MODE_TRUE_FG>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_256_FG: launch_cells_images<ACHIP_MODE_256_FG>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_16_FG: launch_cells_images<ACHIP_MODE_16_FG>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_TRUE_BG: launch_cells_images<ACHIP_MODE_TRUE_BG>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_HB_TRUE: launch_cells_images<ACHIP_MODE_HB_TRUE>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_HB_256: launch_cells_images<ACHIP_MODE_HB_256>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_HB_16: launch_cells_images<ACHIP_MODE_HB_16>(p, a, c, n, cells, status, s); break;
+  case ACHIP_MODE_HB_MONO: launch_cells_images<ACHIP_MODE_HB_MONO>(p, a, c, n, cells, status, s); break;
   default: return (int)hipErrorInvalidValue;
   }
   return (int)hipGetLastError();

@@ -97,6 +97,48 @@ static inline const char *raster_images_check(int mode, const char *palette, con
   return NULL;
 }
 
+/* The same for images_set_composites: a frame may carry comp (a device-visible achip_composite_t the host cannot read, as a plan
+ * takes it), and then its src is not read, src_w x src_h is the canvas the ratios were made for and the source-extent check has
+ * nothing to measure; every other rule is the plain frame's.  *composites (optional): how many frames carry one. */
+static inline const char *raster_images_composites_check(int mode, const char *palette, const achip_frame_t *frames, int n,
+                                                         int max_frames, int *bad, int *composites) {
+  if (bad)
+    *bad = -1;
+  if (composites)
+    *composites = 0;
+  if (mode < ACHIP_MODE_MONO || mode > ACHIP_MODE_HB_MONO)
+    return "mode outside 0..8 (the dithered mode stays on the text path)";
+  const char *why = raster_images_palette_check(palette);
+  if (why)
+    return why;
+  if (!frames || n < 1 || n > max_frames)
+    return "no frames, or their number outside 1..max_frames";
+  int with_comp = 0;
+  for (int i = 0; i < n; i++) {
+    const achip_frame_t *f = &frames[i];
+    if (bad)
+      *bad = i;
+    if (!f->src && !f->comp)
+      return "a descriptor with neither a source nor a composite";
+    if (f->src_w < 1 || f->src_h < 1 || f->out_w < 1 || f->out_h < 1 || f->pad_left < 0 || f->pad_top < 0)
+      return "a size below 1, or a negative padding";
+    if (!achip_desc_ratios_ok(f))
+      return "(out_w - 1) * x_ratio or (out_h - 1) * y_ratio reaches 2^32";
+    if (!f->comp && !achip_desc_extent_ok(f))
+      return "a source that spans 4 GiB or more";
+    if (f->ops & ACHIP_OP_DITHER_MASK)
+      return "a dither bit in ops";
+    if ((f->ops & ACHIP_OP_TINT) && (f->ops & ACHIP_OP_FG_OVERRIDE))
+      return "TINT and FG_OVERRIDE together";
+    with_comp += f->comp != NULL;
+  }
+  if (bad)
+    *bad = -1;
+  if (composites)
+    *composites = with_comp;
+  return NULL;
+}
+
 /* the parse kernel's lookup: the slot of a codepoint in the atlas' ascending codepoints */
 static inline uint32_t raster_images_slot(const uint32_t *codepoints, int n_glyphs, int matrix_map, uint32_t cp) {
   if (cp == 0u || cp == 0x20u)
@@ -155,9 +197,11 @@ static inline uint32_t raster_images_tables(int mode, const char *palette, const
 static inline size_t raster_images_at_frames(void) { return (sizeof(raster_img_tables_t) + 15u) & ~(size_t)15u; }
 static inline size_t raster_images_bytes(int frames) { return raster_images_at_frames() + (size_t)frames * sizeof(achip_frame_t); }
 
-/* the launcher (raster.hip); returns a hipError_t.  cells: n * rows * cols of the handle; 1 <= n <= the frames behind a->frames */
-int raster_launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int n, raster_cell_t *cells, uint32_t *status,
-                               void *stream);
+/* the launcher (raster.hip); returns a hipError_t.  cells: n * rows * cols of the handle; 1 <= n <= the frames behind a->frames;
+ * composites: some frame of the set carries comp (the kernel form with the staged composite sampler), 0: none does (a composite
+ * frame in such a launch would be read as a plain one -- the host never lets that happen) */
+int raster_launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int composites, int n, raster_cell_t *cells,
+                               uint32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,19 @@
  *   HB_256 / HB_16      runs are cells of equal quantised pairs, and the run's FIRST cell decides by its raw bytes whether the
  *                       run is transparent.  Only a cell quantised like black on both halves can belong to such a run; it
  *                       walks left to its run's first cell.
+ *
+ * Grid composites (images_set_composites): COMP = true is the kernel of a set in which some frame carries comp; COMP = false is
+ * the kernel of every other set, with no barrier and no LDS, as before.  A workgroup whose frame is a composite copies the
+ * 464-byte descriptor and the reciprocals of the two cell sizes into LDS (comp_stage, ACHIP_COMP_LDS_BYTES at offset 0), passes
+ * ONE barrier -- every lane of the workgroup, the idle ones behind the grid's last cell too, which is why those lanes are masked
+ * and not returned early --, reads the descriptor's uniform head once (comp_head) and samples through sample_frame_raw<true, 0>
+ * and sample_finish<true>, the three walks above included; a plain frame of such a set takes the plain sampler.  The staged
+ * sampler and not the global one (sample_composite), although tests/test_composite_boundaries.py holds the two equal: the walks
+ * are chains of dependent samples, and the global sampler makes each of them two divisions and three dependent global loads
+ * (cell size -> tile record -> pixel) where the staged one has a multiply-high, LDS reads and one global request; and it is the
+ * sampler the renderers of these frames use (stream, rows and phase kernels), so text path and this stage read a descriptor the
+ * same way -- its _pad word for every sample outside the tiles included.  Flips and tints do not apply to a composite frame
+ * (sample_frame_raw, sample_finish); FG_OVERRIDE does, as the token builder applies it.
  * Only plain HIP and gfx950_ops.hpp: the same source runs under the CPU emulator (tests/hipemu).
  */
 #pragma once
@@ -36,11 +49,21 @@ namespace raster {
 /* a sample (0x00BBGGRR) as a cell colour (0x00RRGGBB) */
 __device__ inline uint32_t cell_rgb(uint32_t p) { return (p & 0xFFu) << 16 | (p & 0xFF00u) | ((p >> 16) & 0xFFu); }
 
-__device__ inline uint32_t image_sample(const achip_frame_t &f, uint32_t x, uint32_t y) { return px_rgb(sample_frame<false>(f, x, y)); }
+/* Sample (x, y) of the frame.  COMP: the launch may hold composite frames, whose descriptor the workgroup staged at LDS offset 0
+ * (`head`: its wave-uniform fields, comp_head); a plain frame in such a launch takes the plain sampler, as in the renderers. */
+template <bool COMP> __device__ inline uint32_t image_sample(const achip_frame_t &f, const CompHead *head, uint32_t x, uint32_t y) {
+  if (!COMP)
+    return px_rgb(sample_frame<false>(f, x, y));
+  uint32_t kind;
+  const uint32_t v = sample_frame_raw<true, 0>(f, x, y, kind, head);
+  return px_rgb(sample_finish<true>(f, v, kind));
+}
 
 /* TRUE_FG: the pen (as a sample) behind cell (x, y) of the frame's text -- the colour the cell itself shows */
-__device__ inline uint32_t truecolor_pen(const achip_frame_t &f, const uint32_t *__restrict__ slot, bool mixed, uint32_t x, uint32_t y) {
-  const uint32_t p = image_sample(f, x, y);
+template <bool COMP>
+__device__ inline uint32_t truecolor_pen(const achip_frame_t &f, const CompHead *head, const uint32_t *__restrict__ slot, bool mixed,
+                                         uint32_t x, uint32_t y) {
+  const uint32_t p = image_sample<COMP>(f, head, x, y);
   if (!mixed || !(slot[luma601(p)] & RASTER_IMG_ASCII))
     return p; /* every cell sets the pen it needs, or a multi-byte glyph: always its own colour */
   /* a one-byte cell of colour p sets the pen when the one-byte cell before it, multi-byte cells skipped, has another colour
@@ -60,7 +83,7 @@ __device__ inline uint32_t truecolor_pen(const achip_frame_t &f, const uint32_t 
   for (;;) {
     if (!back())
       return p;
-    uint32_t q = image_sample(f, x, y);
+    uint32_t q = image_sample<COMP>(f, head, x, y);
     if (slot[luma601(q)] & RASTER_IMG_ASCII) {
       if (q != p)
         return p;
@@ -70,7 +93,7 @@ __device__ inline uint32_t truecolor_pen(const achip_frame_t &f, const uint32_t 
     do {
       if (!back())
         return p;
-      q = image_sample(f, x, y);
+      q = image_sample<COMP>(f, head, x, y);
     } while (!(slot[luma601(q)] & RASTER_IMG_ASCII));
     return q != p ? p : wide;
   }
@@ -78,7 +101,7 @@ __device__ inline uint32_t truecolor_pen(const achip_frame_t &f, const uint32_t 
 
 template <int MODE> __device__ inline uint32_t indexed_key(uint32_t p) { return MODE == ACHIP_MODE_HB_256 || MODE == ACHIP_MODE_256_FG ? quant256(p) : quant16(p); }
 
-template <int MODE>
+template <int MODE, bool COMP = false>
 __global__ void __launch_bounds__(RASTER_BLOCK)
     cells_images_kernel(const raster_params_t p, const raster_img_args_t a, raster_cell_t *__restrict__ cells, uint32_t *__restrict__ status) {
   constexpr bool HB = mode_is_halfblock(MODE);
@@ -100,69 +123,81 @@ __global__ void __launch_bounds__(RASTER_BLOCK)
     status[fi] = st;
   }
   const uint32_t c = blockIdx.x * RASTER_IMG_CELLS + tid;
-  if (c >= rows * cols)
+  const bool live = c < rows * cols; /* the last workgroup of a grid: lanes behind its cells */
+  if (!COMP && !live)
     return;
-  const uint32_t row = c / cols, col = c - row * cols;
-  raster_cell_t v;
-  v.slot = RASTER_NO_GLYPH;
-  v.fg = p.default_fg;
-  v.bg = p.default_bg;
-  const int32_t ty = (int32_t)row - f.pad_top, x = (int32_t)col - f.pad_left;
-  const bool given = (f.ops & ACHIP_OP_FG_OVERRIDE) != 0u; /* every truecolor foreground SGR carries this colour instead */
-  const uint32_t given_rgb = cell_rgb(f.ops >> ACHIP_OP_TINT_SHIFT);
-  if (ty >= 0 && ty < T && x < f.out_w) {
-    if (x < 0) { /* a pad space: blank, but for the pen no reset has cleared */
-      if (MODE == ACHIP_MODE_TRUE_FG && ty > 0)
-        v.fg = given ? given_rgb : cell_rgb(truecolor_pen(f, slot, a.mixed != 0u, (uint32_t)f.out_w - 1u, (uint32_t)ty - 1u));
-    } else if (!HB) {
-      const uint32_t px = image_sample(f, (uint32_t)x, (uint32_t)ty);
-      const uint32_t Y = luma601(px);
-      v.slot = slot[Y] & 0xFFFFu;
-      if (MODE == ACHIP_MODE_TRUE_FG) {
-        v.fg = given ? given_rgb : a.mixed ? cell_rgb(truecolor_pen(f, slot, true, (uint32_t)x, (uint32_t)ty)) : cell_rgb(px);
-      } else if (MODE == ACHIP_MODE_256_FG || MODE == ACHIP_MODE_16_FG) {
-        v.fg = p.lut[indexed_key<MODE>(px)];
-      } else if (MODE == ACHIP_MODE_TRUE_BG) {
-        v.bg = cell_rgb(px);
-        v.fg = given ? given_rgb : Y < 128u ? 0xFFFFFFu : 0u;
-      }
-    } else {
-      const uint32_t yt = 2u * (uint32_t)ty, yb = yt + 1u;
-      const bool twin = yb >= (uint32_t)f.out_h; /* an odd height: the last row's lower half repeats the upper */
-      const uint32_t pt = image_sample(f, (uint32_t)x, yt);
-      const uint32_t pb = twin ? pt : image_sample(f, (uint32_t)x, yb);
-      if (MODE == ACHIP_MODE_HB_MONO) {
-        const uint32_t lt = (76u * px_r(pt) + 150u * px_g(pt) + 29u * px_b(pt)) >> 8;
-        const uint32_t lb = (76u * px_r(pb) + 150u * px_g(pb) + 29u * px_b(pb)) >> 8;
-        if (lt >= 16u || lb >= 16u)
-          v.slot = fixed[1u + (lt >> 6)];
-      } else if (MODE == ACHIP_MODE_HB_TRUE) {
-        if ((pt | pb) != 0u) {
-          v.slot = fixed[0];
-          v.fg = given ? given_rgb : cell_rgb(pt);
-          v.bg = cell_rgb(pb);
+  CompHead chead = {}; /* the staged descriptor's head: read for the composite frames of a COMP launch only */
+  const CompHead *ch = &chead;
+  if (COMP) { /* every lane reaches the barrier, the idle ones of the last workgroup too; f.comp is uniform per workgroup */
+    if (f.comp)
+      comp_stage<0, RASTER_BLOCK>(f.comp, (int)tid);
+    __syncthreads();
+    if (f.comp)
+      chead = comp_head<0>();
+  }
+  if (live) {
+    const uint32_t row = c / cols, col = c - row * cols;
+    raster_cell_t v;
+    v.slot = RASTER_NO_GLYPH;
+    v.fg = p.default_fg;
+    v.bg = p.default_bg;
+    const int32_t ty = (int32_t)row - f.pad_top, x = (int32_t)col - f.pad_left;
+    const bool given = (f.ops & ACHIP_OP_FG_OVERRIDE) != 0u; /* every truecolor foreground SGR carries this colour instead */
+    const uint32_t given_rgb = cell_rgb(f.ops >> ACHIP_OP_TINT_SHIFT);
+    if (ty >= 0 && ty < T && x < f.out_w) {
+      if (x < 0) { /* a pad space: blank, but for the pen no reset has cleared */
+        if (MODE == ACHIP_MODE_TRUE_FG && ty > 0)
+          v.fg = given ? given_rgb : cell_rgb(truecolor_pen<COMP>(f, ch, slot, a.mixed != 0u, (uint32_t)f.out_w - 1u, (uint32_t)ty - 1u));
+      } else if (!HB) {
+        const uint32_t px = image_sample<COMP>(f, ch, (uint32_t)x, (uint32_t)ty);
+        const uint32_t Y = luma601(px);
+        v.slot = slot[Y] & 0xFFFFu;
+        if (MODE == ACHIP_MODE_TRUE_FG) {
+          v.fg = given ? given_rgb : a.mixed ? cell_rgb(truecolor_pen<COMP>(f, ch, slot, true, (uint32_t)x, (uint32_t)ty)) : cell_rgb(px);
+        } else if (MODE == ACHIP_MODE_256_FG || MODE == ACHIP_MODE_16_FG) {
+          v.fg = p.lut[indexed_key<MODE>(px)];
+        } else if (MODE == ACHIP_MODE_TRUE_BG) {
+          v.bg = cell_rgb(px);
+          v.fg = given ? given_rgb : Y < 128u ? 0xFFFFFFu : 0u;
         }
       } else {
-        const uint32_t black = indexed_key<MODE>(0u);
-        const uint32_t kt = indexed_key<MODE>(pt), kb = indexed_key<MODE>(pb);
-        uint32_t head = pt | pb; /* the raw bytes of the run's first cell */
-        if (kt == black && kb == black)
-          for (uint32_t hx = (uint32_t)x; hx > 0u; hx--) {
-            const uint32_t qt = image_sample(f, hx - 1u, yt);
-            const uint32_t qb = twin ? qt : image_sample(f, hx - 1u, yb);
-            if (indexed_key<MODE>(qt) != black || indexed_key<MODE>(qb) != black)
-              break;
-            head = qt | qb;
+        const uint32_t yt = 2u * (uint32_t)ty, yb = yt + 1u;
+        const bool twin = yb >= (uint32_t)f.out_h; /* an odd height: the last row's lower half repeats the upper */
+        const uint32_t pt = image_sample<COMP>(f, ch, (uint32_t)x, yt);
+        const uint32_t pb = twin ? pt : image_sample<COMP>(f, ch, (uint32_t)x, yb);
+        if (MODE == ACHIP_MODE_HB_MONO) {
+          const uint32_t lt = (76u * px_r(pt) + 150u * px_g(pt) + 29u * px_b(pt)) >> 8;
+          const uint32_t lb = (76u * px_r(pb) + 150u * px_g(pb) + 29u * px_b(pb)) >> 8;
+          if (lt >= 16u || lb >= 16u)
+            v.slot = fixed[1u + (lt >> 6)];
+        } else if (MODE == ACHIP_MODE_HB_TRUE) {
+          if ((pt | pb) != 0u) {
+            v.slot = fixed[0];
+            v.fg = given ? given_rgb : cell_rgb(pt);
+            v.bg = cell_rgb(pb);
           }
-        if (head != 0u) {
-          v.slot = fixed[0];
-          v.fg = p.lut[kt];
-          v.bg = p.lut[256u + kb];
+        } else {
+          const uint32_t black = indexed_key<MODE>(0u);
+          const uint32_t kt = indexed_key<MODE>(pt), kb = indexed_key<MODE>(pb);
+          uint32_t head = pt | pb; /* the raw bytes of the run's first cell */
+          if (kt == black && kb == black)
+            for (uint32_t hx = (uint32_t)x; hx > 0u; hx--) {
+              const uint32_t qt = image_sample<COMP>(f, ch, hx - 1u, yt);
+              const uint32_t qb = twin ? qt : image_sample<COMP>(f, ch, hx - 1u, yb);
+              if (indexed_key<MODE>(qt) != black || indexed_key<MODE>(qb) != black)
+                break;
+              head = qt | qb;
+            }
+          if (head != 0u) {
+            v.slot = fixed[0];
+            v.fg = p.lut[kt];
+            v.bg = p.lut[256u + kb];
+          }
         }
       }
     }
+    cells[(uint64_t)fi * rows * cols + c] = v;
   }
-  cells[(uint64_t)fi * rows * cols + c] = v;
 }
 
 } // namespace raster

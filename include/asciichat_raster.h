@@ -151,7 +151,7 @@ int asciichat_raster_draw_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev,
  *   - a mode outside 0..8: ACHIP_MODE_16_DITHER_BG is serial error diffusion and stays on the text path;
  *   - a NULL or empty palette, one that is not well-formed UTF-8, or one with a C0 byte or DEL (the grammar reads those as
  *     controls, not as cells);
- *   - n outside 1..max_frames; a descriptor with comp != NULL (composites stay on the text path) or src == NULL; a size below
+ *   - n outside 1..max_frames; a descriptor with comp != NULL (those go through images_set_composites) or src == NULL; a size below
  *     1 or a negative padding; (out_w - 1) * x_ratio or (out_h - 1) * y_ratio at 2^32 or above; a source spanning 4 GiB or
  *     more; ops with a dither bit, or with both ACHIP_OP_TINT and ACHIP_OP_FG_OVERRIDE.
  * The descriptors and the mode's glyph table go to the device through a pinned copy the handle owns, asynchronously on
@@ -167,6 +167,21 @@ int asciichat_raster_draw_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev,
  * images_set.  Asynchronous on `stream`: never synchronise, allocate nothing. */
 int asciichat_raster_images_set(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames, int n,
                                 void *stream);
+/* images_set for the view a server shows every client of a call: the same arguments, lifetime and stream rules, but a frame may
+ * carry comp -- a DEVICE-visible achip_composite_t exactly as a plan takes it, from asciichat_hip_composite_upload or from
+ * asciichat_hip_grid_composite_dev() (asciichat_hip.h); the grid pokes its source pointers on the device per tick, so one set
+ * serves every tick.  A set made by either entry replaces the last one, and cells_from_images, run_images and
+ * run_images_yuv420 run whichever is current.  For a composite frame src is not read, src_w x src_h is the canvas the ratios
+ * were made for (achip_frame_setup over the W x 2H canvas), flips and tints are ignored and FG_OVERRIDE acts, as in the
+ * renderers; pixels outside every tile are black.  Plain and composite frames mix in one set, as in a plan.  The checks are
+ * images_set's, except that comp is taken, a frame needs src or comp, and a composite frame has no source extent to check; every
+ * set taken here is one asciichat_hip_plan_create takes, and cells, images and status are byte for byte those of plan_render
+ * followed by run() / run_yuv420().  A set without a composite frame costs what images_set's does.
+ * The descriptor is read by the staged sampler the renderers use: its _pad word must be zero (it is the pixel of every sample
+ * outside the tiles) and a grid without cells (cell_w, cell_h, cols or rows of 0) must have n_src == 0.  composite_upload
+ * guarantees both; a descriptor placed on the device by other means must keep them. */
+int asciichat_raster_images_set_composites(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames, int n,
+                                           void *stream);
 int asciichat_raster_cells_from_images(asciichat_raster_t *r, int n, uint32_t *status_dev, void *stream);
 int asciichat_raster_run_images(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, uint32_t *status_dev,
                                 void *stream);
