@@ -11,3 +11,4 @@ The directory name contains a hyphen, so import it with the helper in __graft_en
 from .binding import *  # noqa: F401,F403
 from . import distributed  # noqa: F401
 from .raster import *  # noqa: F401,F403  (libasciichat_raster.so: loaded at the first Raster, not here)
+from .yuv import *  # noqa: F401,F403  (libasciichat_yuv.so: loaded at the first Yuv or yuv_convert, not here)
