@@ -12,3 +12,4 @@ from .binding import *  # noqa: F401,F403
 from . import distributed  # noqa: F401
 from .raster import *  # noqa: F401,F403  (libasciichat_raster.so: loaded at the first Raster, not here)
 from .yuv import *  # noqa: F401,F403  (libasciichat_yuv.so: loaded at the first Yuv or yuv_convert, not here)
+from .yuvgrid import *  # noqa: F401,F403  (libasciichat_yuvgrid.so: loaded at the first YuvGrid, not here)

@@ -76,7 +76,7 @@ int asciichat_yuv_create(asciichat_yuv_t **h, int max_frames);
 
 /* The tick's sources and, with them, the descriptors achip_frame_setup() made for them (n of each, 1 <= n <= max_frames).
  * Of frames[i], src and src_stride are not read; src_w x src_h must equal source i's size; achip_frame_ratios_ok's rule must
- * hold; a descriptor with comp is refused with ERR_NOT_SUPPORTED (YUV tiles of a composite go through run_whole first).
+ * hold; a descriptor with comp is refused with ERR_NOT_SUPPORTED (the YUV tiles of a composite: asciichat_yuvgrid.h).
  * frames may be NULL: the handle then serves run_whole only, and run / render_frames refuse.
  * Checked on the host before anything changes: a refused call leaves the handle as it was.  Sources and descriptors travel in
  * one pinned block the handle owns, by one asynchronous copy on `stream`; should the block still be in flight from the set
