@@ -80,7 +80,8 @@ inline uint32_t agent_arrive_u32(uint32_t *p) {
   *reinterpret_cast<volatile uint32_t *>(p) = old + 1u;
   return old;
 }
-template <int N> inline void spin_nap() {}
+/* a lane that polled, found nothing and waits: counted, so that a test can tell whether a wait path ran (hip_emu.h) */
+template <int N> inline void spin_nap() { hipemu::g_naps++; }
 inline void wg_store_u32(uint32_t *p, uint32_t v) { *reinterpret_cast<volatile uint32_t *>(p) = v; }
 inline uint32_t wg_load_u32(const uint32_t *p) { return *reinterpret_cast<const volatile uint32_t *>(p); }
 inline uint32_t wg_fetch_add_u32(uint32_t *p, uint32_t v) {
