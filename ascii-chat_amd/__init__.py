@@ -13,3 +13,4 @@ from . import distributed  # noqa: F401
 from .raster import *  # noqa: F401,F403  (libasciichat_raster.so: loaded at the first Raster, not here)
 from .yuv import *  # noqa: F401,F403  (libasciichat_yuv.so: loaded at the first Yuv or yuv_convert, not here)
 from .yuvgrid import *  # noqa: F401,F403  (libasciichat_yuvgrid.so: loaded at the first YuvGrid, not here)
+from .yuvbox import *  # noqa: F401,F403  (libasciichat_yuvbox.so: loaded at the first YuvBox or yuvbox_downscale, not here)
