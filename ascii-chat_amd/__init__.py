@@ -14,3 +14,4 @@ from .raster import *  # noqa: F401,F403  (libasciichat_raster.so: loaded at the
 from .yuv import *  # noqa: F401,F403  (libasciichat_yuv.so: loaded at the first Yuv or yuv_convert, not here)
 from .yuvgrid import *  # noqa: F401,F403  (libasciichat_yuvgrid.so: loaded at the first YuvGrid, not here)
 from .yuvbox import *  # noqa: F401,F403  (libasciichat_yuvbox.so: loaded at the first YuvBox or yuvbox_downscale, not here)
+from .yuvboxgrid import *  # noqa: F401,F403  (libasciichat_yuvboxgrid.so: loaded at the first YuvBoxGrid, not here)

@@ -23,6 +23,12 @@
  *   Phase 2, after one barrier, is box_kernel's: 3 * out_w lanes each add their box's columns at pitch 3, divide and store one
  *   byte.  Exactly 3 * out_w * out_h bytes of an image are stored.
  *
+ * The phase-1 functions take a column range [c0, c1), c0 a multiple of four: only the groups and edge columns that touch it are
+ * summed, and the stage starts at column c0 (3 * (x - c0) + c is the word of column x).  They also take the lanes that share the
+ * work (Lanes: this lane's index among `count`) and their stage, and rows [y0, y1) that may be none (the stage then holds
+ * zeros).  box_kernel passes the whole width, the whole workgroup and the whole box; the tile kernel of yuvboxgrid_kernels.hpp a
+ * segment of a row's boxes, and where that leaves lanes idle, a slice of the box's rows per part of the workgroup.
+ *
  * Row offsets are 64-bit, sums are 32-bit (an all-white 3840 x 2160 frame averaged to 1 x 1 sums to 2 115 072 000; with n / 2
  * added still below 2^32): no 16-bit partial sums, nothing to flush.  No atomics, no inline assembly, no scratch.
  * Only plain HIP and gfx950_ops.hpp: the same source runs under the CPU emulator (tests/hipemu).
@@ -68,31 +74,50 @@ __device__ inline void add_four(uint32_t (&acc)[12], uint32_t yw, const uint32_t
     add_pixel(acc + 3 * k, yuv_rgb((yw >> (8 * k)) & 0xFFu, u[k >> 1], v[k >> 1]));
 }
 
-/* a group's sums to the stage: columns 4 * g .. 4 * g + 3, three words each */
-__device__ inline void stage_group(uint32_t g, const uint32_t (&acc)[12]) {
-  uint4 *slot = reinterpret_cast<uint4 *>(ACHIP_SMEM) + 3u * g;
+/* the lanes that share a range of columns and rows, and where their sums go (16-aligned LDS) */
+struct Lanes {
+  uint32_t lane, count; /* count >= 3: the edge columns take a lane each */
+  uint32_t *stage;
+};
+__device__ inline Lanes whole_workgroup() { return Lanes{threadIdx.x, kBlock, reinterpret_cast<uint32_t *>(ACHIP_SMEM)}; }
+
+/* a group's sums to the stage: columns 4 * g .. 4 * g + 3 of a stage that starts at group g = 0, three words each */
+__device__ inline void stage_group(uint32_t *stage, uint32_t g, const uint32_t (&acc)[12]) {
+  uint4 *slot = reinterpret_cast<uint4 *>(stage) + 3u * g;
   slot[0] = make_uint4(acc[0], acc[1], acc[2], acc[3]);
   slot[1] = make_uint4(acc[4], acc[5], acc[6], acc[7]);
   slot[2] = make_uint4(acc[8], acc[9], acc[10], acc[11]);
 }
 
-/* the columns behind the last whole group, one lane each, pixel by pixel */
-__device__ inline void edge_columns(const asciichat_yuv_source_t &s, uint32_t groups, uint32_t y0, uint32_t y1) {
-  const uint32_t x = 4u * groups + threadIdx.x;
-  if (x >= (uint32_t)s.width)
+/* the columns behind the last whole group (groups = width / 4) that lie below c1, one lane each, pixel by pixel */
+__device__ inline void edge_columns(const asciichat_yuv_source_t &s, uint32_t groups, uint32_t y0, uint32_t y1, uint32_t c0, uint32_t c1,
+                                    const Lanes &w) {
+  const uint32_t x = 4u * groups + w.lane;
+  if (x >= (uint32_t)s.width || x >= c1)
     return;
   const yuv_layout_t l = yuv_layout(&s);
   uint32_t acc[3] = {0u, 0u, 0u};
   for (uint32_t r = y0; r < y1; r++)
     add_pixel(acc, yuv_rgb(global_of(l.y_plane)[yuv_at_y(&l, (int32_t)x, (int32_t)r)], global_of(l.u_plane)[yuv_at_u(&l, (int32_t)x, (int32_t)r)],
                            global_of(l.v_plane)[yuv_at_v(&l, (int32_t)x, (int32_t)r)]));
-  uint32_t *sums = reinterpret_cast<uint32_t *>(ACHIP_SMEM);
-  sums[3u * x] = acc[0], sums[3u * x + 1u] = acc[1], sums[3u * x + 2u] = acc[2];
+  uint32_t *sums = w.stage;
+  sums[3u * (x - c0)] = acc[0], sums[3u * (x - c0) + 1u] = acc[1], sums[3u * (x - c0) + 2u] = acc[2]; /* (c0 <= 4 * groups) */
 }
 
-/* 4:2:0: sums[3 * x + c] = the sum over rows [y0, y1) of channel c of the converted pixel (x, row) */
-template <int FORMAT> __device__ inline void planar_sums(const asciichat_yuv_source_t &s, uint32_t y0, uint32_t y1) {
+/* the whole groups that touch columns [c0, c1): [c0 / 4, *last) */
+__device__ inline uint32_t first_group(uint32_t groups, uint32_t c0, uint32_t c1, uint32_t *last) {
+  const uint32_t end = (c1 + 3u) / 4u;
+  *last = end < groups ? end : groups;
+  return c0 / 4u;
+}
+
+/* 4:2:0: sums[3 * (x - c0) + c] = the sum over rows [y0, y1) of channel c of the converted pixel (x, row), for the columns of
+ * the groups that touch [c0, c1) (c0 a multiple of four, c0 < c1 <= width) */
+template <int FORMAT> __device__ inline void planar_sums(const asciichat_yuv_source_t &s, uint32_t y0, uint32_t y1, uint32_t c0, uint32_t c1,
+                                                      const Lanes &w) {
   const uint32_t groups = (uint32_t)s.width / 4u;
+  uint32_t last;
+  const uint32_t first = first_group(groups, c0, c1, &last);
   const ACHIP_GLOBAL uint8_t *yp = global_of(s.plane[0]);
   const ACHIP_GLOBAL uint8_t *up = global_of(s.plane[1]);
   const ACHIP_GLOBAL uint8_t *vp = global_of(s.plane[FORMAT == ASCIICHAT_YUV_I420 ? 2 : 1]);
@@ -100,7 +125,7 @@ template <int FORMAT> __device__ inline void planar_sums(const asciichat_yuv_sou
   const bool y_aligned = multiple_of(s.plane[0], s.stride[0], 4u);
   const bool u_aligned = multiple_of(s.plane[1], s.stride[1], FORMAT == ASCIICHAT_YUV_I420 ? 2u : 4u);
   const bool v_aligned = FORMAT == ASCIICHAT_YUV_I420 ? multiple_of(s.plane[2], s.stride[2], 2u) : u_aligned;
-  for (uint32_t g = threadIdx.x; g < groups; g += kBlock) {
+  for (uint32_t g = first + w.lane; g < last; g += w.count) {
     uint32_t acc[12];
 #pragma unroll
     for (int k = 0; k < 12; k++)
@@ -121,7 +146,7 @@ template <int FORMAT> __device__ inline void planar_sums(const asciichat_yuv_sou
       add_four(acc, load_u32(yp + (int64_t)r * ys + 4u * g, y_aligned), u, v);
     };
     uint32_t r = y0;
-    if (r & 1u) /* (y1 > y0 always) */
+    if ((r & 1u) && r < y1)
       one_row(r++);
 #pragma unroll 2
     for (; r + 2u <= y1; r += 2u) {
@@ -133,18 +158,21 @@ template <int FORMAT> __device__ inline void planar_sums(const asciichat_yuv_sou
     }
     if (r < y1)
       one_row(r);
-    stage_group(g, acc);
+    stage_group(w.stage, g - first, acc);
   }
-  edge_columns(s, groups, y0, y1);
+  edge_columns(s, groups, y0, y1, c0, c1, w);
 }
 
 /* 4:2:2: the same sums from rows of packed pairs -- UYVY: U Y0 V Y1; YUYV: Y0 U Y1 V */
-template <int FORMAT> __device__ inline void packed_sums(const asciichat_yuv_source_t &s, uint32_t y0, uint32_t y1) {
+template <int FORMAT> __device__ inline void packed_sums(const asciichat_yuv_source_t &s, uint32_t y0, uint32_t y1, uint32_t c0, uint32_t c1,
+                                                      const Lanes &w) {
   const uint32_t groups = (uint32_t)s.width / 4u;
+  uint32_t last;
+  const uint32_t first = first_group(groups, c0, c1, &last);
   const ACHIP_GLOBAL uint8_t *p0 = global_of(s.plane[0]);
   const int64_t stride = s.stride[0];
   const bool aligned = multiple_of(s.plane[0], s.stride[0], 4u);
-  for (uint32_t g = threadIdx.x; g < groups; g += kBlock) {
+  for (uint32_t g = first + w.lane; g < last; g += w.count) {
     uint32_t acc[12];
 #pragma unroll
     for (int k = 0; k < 12; k++)
@@ -165,9 +193,19 @@ template <int FORMAT> __device__ inline void packed_sums(const asciichat_yuv_sou
         }
       }
     }
-    stage_group(g, acc);
+    stage_group(w.stage, g - first, acc);
   }
-  edge_columns(s, groups, y0, y1); /* (an even width: two columns, or none) */
+  edge_columns(s, groups, y0, y1, c0, c1, w); /* (an even width: two columns, or none) */
+}
+
+/* the sums of columns [c0, c1) of rows [y0, y1) of a source into the stage, by its format */
+__device__ inline void column_sums(const asciichat_yuv_source_t &s, uint32_t y0, uint32_t y1, uint32_t c0, uint32_t c1, const Lanes &w) {
+  switch (s.format) { /* a format outside the four stores nothing defined: the host refuses it */
+  case ASCIICHAT_YUV_I420: planar_sums<ASCIICHAT_YUV_I420>(s, y0, y1, c0, c1, w); break;
+  case ASCIICHAT_YUV_NV12: planar_sums<ASCIICHAT_YUV_NV12>(s, y0, y1, c0, c1, w); break;
+  case ASCIICHAT_YUV_YUYV: packed_sums<ASCIICHAT_YUV_YUYV>(s, y0, y1, c0, c1, w); break;
+  default: packed_sums<ASCIICHAT_YUV_UYVY>(s, y0, y1, c0, c1, w); break;
+  }
 }
 
 /* workgroup b: image b / rows_per_image, stored row b % rows_per_image (rows beyond the image's out_h: nothing to do).
@@ -186,12 +224,7 @@ __global__ void __launch_bounds__(YUV_BLOCK)
     return;
   uint32_t y0, y1;
   yuvbox_bounds(src_h, out_h, (it.flips & ACHIP_OP_FLIP_Y) ? out_h - 1u - y : y, &y0, &y1);
-  switch (it.src.format) { /* a format outside the four stores nothing defined: the host refuses it */
-  case ASCIICHAT_YUV_I420: planar_sums<ASCIICHAT_YUV_I420>(it.src, y0, y1); break;
-  case ASCIICHAT_YUV_NV12: planar_sums<ASCIICHAT_YUV_NV12>(it.src, y0, y1); break;
-  case ASCIICHAT_YUV_YUYV: packed_sums<ASCIICHAT_YUV_YUYV>(it.src, y0, y1); break;
-  default: packed_sums<ASCIICHAT_YUV_UYVY>(it.src, y0, y1); break;
-  }
+  column_sums(it.src, y0, y1, 0u, src_w, whole_workgroup());
   __syncthreads();
   const uint32_t *sums = reinterpret_cast<const uint32_t *>(ACHIP_SMEM);
   uint8_t *out = images + (uint64_t)image * pitch + (uint64_t)y * (3u * out_w);

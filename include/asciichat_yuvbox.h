@@ -20,8 +20,8 @@
  *
  * Opt-in and NOT a parity mode, exactly as the box pass is not: the reference point-samples its sources.  The renderers run
  * over the averaged images give byte for byte what the reference's renderers give over those images; nothing is claimed about
- * the source frames.  Out of scope, as for the two passes it composes: the YUV tiles of a composite (asciichat_yuvgrid.h),
- * BT.709 and full-range matrices, interpolated chroma.
+ * the source frames.  The YUV tiles of a composite have the same rule in a library of their own (asciichat_yuvboxgrid.h).  Out
+ * of scope, as for the two passes it composes: BT.709 and full-range matrices, interpolated chroma.
  *
  * A library of its own: it links none of libasciichat_hip.so, libasciichat_raster.so, libasciichat_yuv.so and
  * libasciichat_yuvgrid.so and shares only achip_types.h and asciichat_yuv.h (the source structure, the formats, the error-code

@@ -67,7 +67,7 @@ int asciichat_yuvgrid_run(asciichat_yuvgrid_t *g, uint8_t *tiles_dev, void *stre
  * with asciichat_hip_composite_upload once per geometry; per tick the sequence is set, run, plan_render on one stream.  A
  * rewritten slot is never flipped or tinted: the composite samplers do neither.  asciichat_hip_box_composites over rewritten
  * descriptors averages each source to its tile, so an identity tile stays the point-sampled tile -- not the average over the
- * whole frame; for that, convert with asciichat_yuv_run_whole. */
+ * whole frame; for that, switch the prefix: asciichat_yuvboxgrid_* (asciichat_yuvboxgrid.h) is this interface over averaged tiles. */
 int asciichat_yuvgrid_composites(const asciichat_yuvgrid_t *g, const uint8_t *tiles_dev, achip_composite_t *comps_out);
 
 void asciichat_yuvgrid_destroy(asciichat_yuvgrid_t *g);
