@@ -276,7 +276,11 @@ static int images_stage(asciichat_raster_t *h, int mode, const char *palette_cha
     return rc;
   h->img_dma_queued = 0;
   raster_img_tables_t *t = (raster_img_tables_t *)h->img_pinned;
-  const uint32_t mixed = raster_images_tables(mode, palette_chars, h->codepoints_host, h->p.n_glyphs, h->p.matrix_map, t);
+  uint32_t mixed = 0u;
+  if (mode == ACHIP_MODE_16_DITHER_BG) /* (images_set_dithered alone comes here with this mode) */
+    raster_images_dither_tables(palette_chars, h->codepoints_host, h->p.n_glyphs, h->p.matrix_map, t);
+  else
+    mixed = raster_images_tables(mode, palette_chars, h->codepoints_host, h->p.n_glyphs, h->p.matrix_map, t);
   memcpy(h->img_pinned + raster_images_at_frames(), frames, (size_t)n * sizeof(achip_frame_t));
   h->img_n = 0; /* (should the copy fail, nothing is set) */
   rc = hip_check(hipMemcpyAsync(h->img_dev, h->img_pinned, raster_images_bytes(n), hipMemcpyHostToDevice, (hipStream_t)stream),
@@ -319,6 +323,16 @@ int asciichat_raster_images_set_composites(asciichat_raster_t *r, int mode, cons
              : images_stage(h, mode, palette_chars, frames, n, composites, stream);
 }
 
+int asciichat_raster_images_set_dithered(asciichat_raster_t *r, const char *palette_chars, const achip_frame_t *frames, int n, void *stream) {
+  asciichat_raster_t *h = raster_of(r);
+  if (!h)
+    return fail(ASCIICHAT_RASTER_ERR_INVALID_PARAM, "raster_images_set_dithered: not a rasteriser");
+  int bad = -1, composites = 0;
+  const char *why = raster_images_dithered_check(palette_chars, frames, n, h->max_frames, &bad, &composites);
+  return why ? images_refused("raster_images_set_dithered", bad, why)
+             : images_stage(h, ACHIP_MODE_16_DITHER_BG, palette_chars, frames, n, composites, stream);
+}
+
 /* what cells_from_images asks of its arguments; nothing is launched unless it holds */
 static int images_ok(const asciichat_raster_t *h, int n, const uint32_t *status_dev, const char *what) {
   if (!h)
@@ -337,6 +351,8 @@ int asciichat_raster_cells_from_images(asciichat_raster_t *r, int n, uint32_t *s
   const int rc = images_ok(h, n, status_dev, "raster_cells_from_images");
   if (rc)
     return rc;
+  if (h->img.mode == ACHIP_MODE_16_DITHER_BG) /* the current set's kind: made by images_set_dithered */
+    return hip_check((hipError_t)raster_launch_cells_dither(&h->p, &h->img, h->img_comp, n, h->cells, status_dev, stream), "raster dither launch");
   return hip_check((hipError_t)raster_launch_cells_images(&h->p, &h->img, h->img_comp, n, h->cells, status_dev, stream), "raster images launch");
 }
 

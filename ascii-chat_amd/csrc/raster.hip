@@ -1,9 +1,10 @@
-/* raster.hip -- the launchers of the rasteriser (raster_kernels.hpp, raster_yuv_kernels.hpp, raster_images_kernels.hpp); the host
- * side is raster.c. */
+/* raster.hip -- the launchers of the rasteriser (raster_kernels.hpp, raster_yuv_kernels.hpp, raster_images_kernels.hpp,
+ * raster_dither_kernels.hpp); the host side is raster.c. */
 #include <hip/hip_runtime.h>
 
 #include "launch_common.hpp"
 #include "raster.h"
+#include "raster_dither_kernels.hpp"
 #include "raster_images_kernels.hpp"
 #include "raster_kernels.hpp"
 #include "raster_yuv_kernels.hpp"
@@ -90,4 +91,24 @@ extern "C" int raster_launch_cells_images(const raster_params_t *p, const raster
   default: return (int)hipErrorInvalidValue;
   }
   return (int)hipGetLastError();
+}
+
+/* the dithered mode: one workgroup per frame, the band and the error line in dynamic LDS (above 48 KB: announced once) */
+template <bool COMP>
+static hipError_t launch_cells_dither(const raster_params_t *p, const raster_img_args_t *a, int n, raster_cell_t *cells, uint32_t *status,
+                                      hipStream_t s) {
+  const hipError_t e = achip::ensure_dynamic_lds<achip::raster::cells_dither_kernel<COMP>>(RASTER_DITHER_LDS_BYTES);
+  if (e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL((achip::raster::cells_dither_kernel<COMP>), dim3((unsigned)n), dim3(RASTER_BLOCK), RASTER_DITHER_LDS_BYTES, s, *p, *a,
+                     cells, status);
+  return hipGetLastError();
+}
+
+extern "C" int raster_launch_cells_dither(const raster_params_t *p, const raster_img_args_t *a, int composites, int n, raster_cell_t *cells,
+                                          uint32_t *status, void *stream) {
+  if (!p || !a || !a->tables || !a->frames || a->mode != ACHIP_MODE_16_DITHER_BG || n <= 0 || !cells || !status)
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return (int)(composites ? launch_cells_dither<true>(p, a, n, cells, status, s) : launch_cells_dither<false>(p, a, n, cells, status, s));
 }

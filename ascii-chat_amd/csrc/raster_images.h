@@ -15,15 +15,22 @@ extern "C" {
 #define RASTER_IMG_CELLS RASTER_BLOCK /* cells of the grid per workgroup: one lane each */
 #define RASTER_IMG_ASCII 0x10000u     /* a table entry whose glyph is one byte below 0x80 (the truecolor pen rule) */
 
+/* the dithered mode (images_set_dithered, raster_dither_kernels.hpp): one workgroup per frame */
+#define RASTER_DITHER_MAX_W ASCIICHAT_RASTER_MAX_COLS /* out_w a frame may have: the kernel's error line holds 3 x int per column */
+#define RASTER_DITHER_CAP 16384                       /* samples of a band of text rows in LDS */
+/* the launch's dynamic LDS: the staged composite descriptor (480 bytes), the error line, the band */
+#define RASTER_DITHER_LDS_BYTES (480 + 12 * RASTER_DITHER_MAX_W + 4 * RASTER_DITHER_CAP)
+
 /* what a mode's cells look up: the glyph of a luminance as an atlas slot, and the slots of the half-block modes' glyphs */
 typedef struct {
-  uint32_t slot[256]; /* Y -> slot (RASTER_NO_GLYPH: the atlas lacks it, or it is a space) | RASTER_IMG_ASCII */
+  uint32_t slot[256]; /* Y -> slot (RASTER_NO_GLYPH: the atlas lacks it, or it is a space) | RASTER_IMG_ASCII; the dithered mode:
+                         the slot of cache[Y] | the slot of cache[ramp[Y >> 2]] << 16, one table for its three styles */
   uint32_t fixed[8];  /* [0] U+2580, [1..3] U+2591 U+2592 U+2593, [4] U+2588; the rest 0 */
 } raster_img_tables_t;
 
 /* the last images_set of a handle, by value in the kernel arguments */
 typedef struct {
-  int32_t mode;                      /* ACHIP_MODE_* 0..8 */
+  int32_t mode;                      /* ACHIP_MODE_* 0..8, or ACHIP_MODE_16_DITHER_BG for a set made by images_set_dithered */
   uint32_t mixed;                    /* TRUE_FG: the palette holds one-byte and multi-byte glyphs, so a pen can outlive its cell */
   const raster_img_tables_t *tables; /* device */
   const achip_frame_t *frames;       /* device, as many as were set */
@@ -67,7 +74,7 @@ static inline const char *raster_images_check(int mode, const char *palette, con
   if (bad)
     *bad = -1;
   if (mode < ACHIP_MODE_MONO || mode > ACHIP_MODE_HB_MONO)
-    return "mode outside 0..8 (the dithered mode stays on the text path)";
+    return "mode outside 0..8 (the dithered mode goes through images_set_dithered)";
   const char *why = raster_images_palette_check(palette);
   if (why)
     return why;
@@ -107,7 +114,7 @@ static inline const char *raster_images_composites_check(int mode, const char *p
   if (composites)
     *composites = 0;
   if (mode < ACHIP_MODE_MONO || mode > ACHIP_MODE_HB_MONO)
-    return "mode outside 0..8 (the dithered mode stays on the text path)";
+    return "mode outside 0..8 (the dithered mode goes through images_set_dithered)";
   const char *why = raster_images_palette_check(palette);
   if (why)
     return why;
@@ -128,6 +135,48 @@ static inline const char *raster_images_composites_check(int mode, const char *p
       return "a source that spans 4 GiB or more";
     if (f->ops & ACHIP_OP_DITHER_MASK)
       return "a dither bit in ops";
+    if ((f->ops & ACHIP_OP_TINT) && (f->ops & ACHIP_OP_FG_OVERRIDE))
+      return "TINT and FG_OVERRIDE together";
+    with_comp += f->comp != NULL;
+  }
+  if (bad)
+    *bad = -1;
+  if (composites)
+    *composites = with_comp;
+  return NULL;
+}
+
+/* The same for images_set_dithered, whose mode is implied (ACHIP_MODE_16_DITHER_BG): images_set_composites' rules, except that
+ * ops may carry the dither style bits -- none, DITHER_FG, or DITHER_FG | DITHER_RAMP; DITHER_RAMP alone names no form of the
+ * renderer --, and out_w is bounded by RASTER_DITHER_MAX_W, which sizes the kernel's error line. */
+static inline const char *raster_images_dithered_check(const char *palette, const achip_frame_t *frames, int n, int max_frames, int *bad,
+                                                       int *composites) {
+  if (bad)
+    *bad = -1;
+  if (composites)
+    *composites = 0;
+  const char *why = raster_images_palette_check(palette);
+  if (why)
+    return why;
+  if (!frames || n < 1 || n > max_frames)
+    return "no frames, or their number outside 1..max_frames";
+  int with_comp = 0;
+  for (int i = 0; i < n; i++) {
+    const achip_frame_t *f = &frames[i];
+    if (bad)
+      *bad = i;
+    if (!f->src && !f->comp)
+      return "a descriptor with neither a source nor a composite";
+    if (f->src_w < 1 || f->src_h < 1 || f->out_w < 1 || f->out_h < 1 || f->pad_left < 0 || f->pad_top < 0)
+      return "a size below 1, or a negative padding";
+    if (f->out_w > RASTER_DITHER_MAX_W)
+      return "out_w above 1024 (no grid shows such a row)";
+    if (!achip_desc_ratios_ok(f))
+      return "(out_w - 1) * x_ratio or (out_h - 1) * y_ratio reaches 2^32";
+    if (!f->comp && !achip_desc_extent_ok(f))
+      return "a source that spans 4 GiB or more";
+    if ((f->ops & ACHIP_OP_DITHER_MASK) == ACHIP_OP_DITHER_RAMP)
+      return "DITHER_RAMP without DITHER_FG";
     if ((f->ops & ACHIP_OP_TINT) && (f->ops & ACHIP_OP_FG_OVERRIDE))
       return "TINT and FG_OVERRIDE together";
     with_comp += f->comp != NULL;
@@ -193,6 +242,22 @@ static inline uint32_t raster_images_tables(int mode, const char *palette, const
   return mode == ACHIP_MODE_TRUE_FG && ascii && wide ? 1u : 0u;
 }
 
+/* The table of a checked palette for the dithered mode, over an atlas' codepoints: entry Y holds the slot of cache[Y] (the
+ * background form and DITHER_FG) in bits 15..0 and the slot of cache[ramp[Y >> 2]] (DITHER_FG | DITHER_RAMP) in bits 31..16;
+ * a style is a frame's, so one table serves a set that mixes them. */
+static inline void raster_images_dither_tables(const char *palette, const uint32_t *codepoints, int n_glyphs, int matrix_map,
+                                               raster_img_tables_t *t) {
+  achip_lut_t lut;
+  memset(t, 0, sizeof(*t));
+  if (achip_desc_lut_build(palette, &lut) != 0)
+    return;
+  for (int y = 0; y < 256; y++) {
+    const uint32_t plain = raster_images_slot(codepoints, n_glyphs, matrix_map, raster_images_codepoint(lut.glyph[y]));
+    const uint32_t ramp = raster_images_slot(codepoints, n_glyphs, matrix_map, raster_images_codepoint(lut.glyph[lut.ramp[y >> 2]]));
+    t->slot[y] = plain | ramp << 16;
+  }
+}
+
 /* where the handle keeps a set: the table, then max_frames descriptors, in one block on the device and one pinned on the host */
 static inline size_t raster_images_at_frames(void) { return (sizeof(raster_img_tables_t) + 15u) & ~(size_t)15u; }
 static inline size_t raster_images_bytes(int frames) { return raster_images_at_frames() + (size_t)frames * sizeof(achip_frame_t); }
@@ -201,6 +266,10 @@ static inline size_t raster_images_bytes(int frames) { return raster_images_at_f
  * composites: some frame of the set carries comp (the kernel form with the staged composite sampler), 0: none does (a composite
  * frame in such a launch would be read as a plain one -- the host never lets that happen) */
 int raster_launch_cells_images(const raster_params_t *p, const raster_img_args_t *a, int composites, int n, raster_cell_t *cells,
+                               uint32_t *status, void *stream);
+
+/* the dithered mode's launcher (raster.hip), one workgroup per frame; a->mode is ACHIP_MODE_16_DITHER_BG, the rest as above */
+int raster_launch_cells_dither(const raster_params_t *p, const raster_img_args_t *a, int composites, int n, raster_cell_t *cells,
                                uint32_t *status, void *stream);
 
 #ifdef __cplusplus

@@ -58,6 +58,7 @@ def raster_lib():
                             ("asciichat_raster_draw_yuv420", ci, [vp, ci, vp, sz, ci, vp]),
                             ("asciichat_raster_images_set", ci, [vp, ci, C.c_char_p, vp, ci, vp]),
                             ("asciichat_raster_images_set_composites", ci, [vp, ci, C.c_char_p, vp, ci, vp]),
+                            ("asciichat_raster_images_set_dithered", ci, [vp, C.c_char_p, vp, ci, vp]),
                             ("asciichat_raster_cells_from_images", ci, [vp, ci, vp, vp]),
                             ("asciichat_raster_run_images", ci, [vp, ci, vp, sz, vp, vp]),
                             ("asciichat_raster_run_images_yuv420", ci, [vp, ci, vp, sz, ci, vp, vp]),
@@ -139,7 +140,7 @@ class Raster:
     def set_images(self, mode, palette, frames, stream=0):
         """the frames the *_images methods work on: mode MODE_* 0..8, the renderers' palette, a list (or ctypes array) of
         binding.Frame with device-visible sources; checked on the host, copied asynchronously on `stream` (the handle's one
-        stream).  No composites (set_images_composites takes those), no dithered mode: that stays on the text path"""
+        stream).  No composites (set_images_composites takes those), no dithered mode (set_images_dithered takes that)"""
         from .binding import Frame
         arr = frames if isinstance(frames, C.Array) else (Frame * max(1, len(frames)))(*frames)
         p = palette.encode("utf-8") if isinstance(palette, str) else palette
@@ -150,13 +151,24 @@ class Raster:
     def set_images_composites(self, mode, palette, frames, stream=0):
         """set_images for grid composites: a frame may carry comp, a device-visible composite descriptor as a Plan takes it
         (asciichat_hip_composite_upload, asciichat_hip_grid_composite_dev); its src is not read.  Plain and composite frames mix;
-        replaces the last set of either kind.  The dithered mode stays on the text path"""
+        replaces the last set of any kind.  The dithered mode is refused here too: set_images_dithered takes it"""
         from .binding import Frame
         arr = frames if isinstance(frames, C.Array) else (Frame * max(1, len(frames)))(*frames)
         p = palette.encode("utf-8") if isinstance(palette, str) else palette
         rc = self.L.asciichat_raster_images_set_composites(self._h, mode, p, C.cast(arr, C.c_void_p), len(frames), stream)
         if rc != 0:
             raise RuntimeError(f"asciichat_raster_images_set_composites failed ({rc}): {self.last_error()}")
+
+    def set_images_dithered(self, palette, frames, stream=0):
+        """set_images for the Floyd-Steinberg renderer (MODE_16_DITHER_BG, implied): plain and composite frames, each in the
+        style its ops carry (achip_frame_set_dither_style: background, foreground, foreground with the ramp glyph), out_w up to
+        1024; replaces the last set of any kind"""
+        from .binding import Frame
+        arr = frames if isinstance(frames, C.Array) else (Frame * max(1, len(frames)))(*frames)
+        p = palette.encode("utf-8") if isinstance(palette, str) else palette
+        rc = self.L.asciichat_raster_images_set_dithered(self._h, p, C.cast(arr, C.c_void_p), len(frames), stream)
+        if rc != 0:
+            raise RuntimeError(f"asciichat_raster_images_set_dithered failed ({rc}): {self.last_error()}")
 
     def cells_from_images(self, n, status_ptr, stream=0):
         """parse()'s counterpart: the cells of frames 0..n-1 of the last set_images, straight from their pixels"""

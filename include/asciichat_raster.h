@@ -148,7 +148,8 @@ int asciichat_raster_draw_yuv420(asciichat_raster_t *r, int n, uint8_t *yuv_dev,
  * images_set is the set-up call: mode is ACHIP_MODE_* 0..8 (achip_types.h), palette_chars the renderers' palette, frames a
  * HOST array of n descriptors (1 <= n <= max_frames) whose src are device-visible.  Everything is checked on the host before
  * anything is copied or launched; ERR_INVALID_PARAM, with the handle's earlier set still in place, for
- *   - a mode outside 0..8: ACHIP_MODE_16_DITHER_BG is serial error diffusion and stays on the text path;
+ *   - a mode outside 0..8: ACHIP_MODE_16_DITHER_BG (mode 9), whose cells depend on the error diffused from every cell before
+ *     them, is refused here and by images_set_composites and goes through images_set_dithered below;
  *   - a NULL or empty palette, one that is not well-formed UTF-8, or one with a C0 byte or DEL (the grammar reads those as
  *     controls, not as cells);
  *   - n outside 1..max_frames; a descriptor with comp != NULL (those go through images_set_composites) or src == NULL; a size below
@@ -182,6 +183,26 @@ int asciichat_raster_images_set(asciichat_raster_t *r, int mode, const char *pal
  * guarantees both; a descriptor placed on the device by other means must keep them. */
 int asciichat_raster_images_set_composites(asciichat_raster_t *r, int mode, const char *palette_chars, const achip_frame_t *frames, int n,
                                            void *stream);
+/* images_set for the Floyd-Steinberg renderer, ACHIP_MODE_16_DITHER_BG -- what a truecolor client in the background render mode
+ * is shown (achip_mode_from_caps).  The mode is implied; images_set and images_set_composites keep refusing mode 9 and every
+ * dither bit in ops, and this entry takes them.  Arguments, lifetime, stream, pinned-copy and allocation rules are those of the
+ * other two set calls; a set made by any of the three replaces the last one, and cells_from_images, run_images and
+ * run_images_yuv420 run whichever is current, their arguments and checks unchanged.  A frame may be plain (src) or a composite
+ * (comp, device-visible, as images_set_composites takes it), both kinds in one set; its ops may carry the style bits of
+ * achip_frame_set_dither_style, a style per frame: none is the background form, ACHIP_OP_DITHER_FG the foreground-only form
+ * with the glyph cache[Y], ACHIP_OP_DITHER_FG | ACHIP_OP_DITHER_RAMP the one with the glyph cache[ramp[Y >> 2]].  Flips and
+ * tints act as in the renderer (not on a composite frame); FG_OVERRIDE is taken and changes nothing, for this mode emits no
+ * truecolor SGR.  The frame's out_w x out_h samples are dithered on the device in the renderer's order and arithmetic (7/3/5/1
+ * sixteenths, each truncated toward zero; what leaves the image is dropped; the clamped value is quantised, the unclamped one
+ * gives the error): columns beyond the grid still feed the row below, rows behind the grid are not computed.  Cells, images,
+ * YUV planes and status are byte for byte those of asciichat_hip_plan_render of the same descriptors in mode 9 followed by
+ * run() / run_yuv420(), for INDEXED_FLAT and INDEXED_XTERM fonts, with and without matrix_map.
+ * ERR_INVALID_PARAM, checked on the host before anything is copied or launched and with the earlier set still in place, for
+ * everything images_set_composites refuses except dither bits, for ACHIP_OP_DITHER_RAMP without ACHIP_OP_DITHER_FG, and --
+ * A BOUND OF THIS ENTRY -- for a frame with out_w > ASCIICHAT_RASTER_MAX_COLS (1024): no handle can show such a row, and the
+ * bound sizes the kernel's error line. */
+int asciichat_raster_images_set_dithered(asciichat_raster_t *r, const char *palette_chars, const achip_frame_t *frames, int n,
+                                         void *stream);
 int asciichat_raster_cells_from_images(asciichat_raster_t *r, int n, uint32_t *status_dev, void *stream);
 int asciichat_raster_run_images(asciichat_raster_t *r, int n, uint8_t *pixels_dev, size_t image_pitch, uint32_t *status_dev,
                                 void *stream);
