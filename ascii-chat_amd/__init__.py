@@ -15,3 +15,4 @@ from .yuv import *  # noqa: F401,F403  (libasciichat_yuv.so: loaded at the first
 from .yuvgrid import *  # noqa: F401,F403  (libasciichat_yuvgrid.so: loaded at the first YuvGrid, not here)
 from .yuvbox import *  # noqa: F401,F403  (libasciichat_yuvbox.so: loaded at the first YuvBox or yuvbox_downscale, not here)
 from .yuvboxgrid import *  # noqa: F401,F403  (libasciichat_yuvboxgrid.so: loaded at the first YuvBoxGrid, not here)
+from .pix import *  # noqa: F401,F403  (libasciichat_pix.so: loaded at the first Pix, pix_convert or pix_downscale, not here)
