@@ -16,3 +16,4 @@ from .yuvgrid import *  # noqa: F401,F403  (libasciichat_yuvgrid.so: loaded at t
 from .yuvbox import *  # noqa: F401,F403  (libasciichat_yuvbox.so: loaded at the first YuvBox or yuvbox_downscale, not here)
 from .yuvboxgrid import *  # noqa: F401,F403  (libasciichat_yuvboxgrid.so: loaded at the first YuvBoxGrid, not here)
 from .pix import *  # noqa: F401,F403  (libasciichat_pix.so: loaded at the first Pix, pix_convert or pix_downscale, not here)
+from .pixgrid import *  # noqa: F401,F403  (libasciichat_pixgrid.so: loaded at the first PixGrid, not here)

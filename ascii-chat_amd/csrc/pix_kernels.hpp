@@ -34,6 +34,10 @@
  *   Phase 2, after one barrier, is box_kernels.hpp's text (restated: it is the body of that kernel, not a function of its
  *   header): 3 * out_w lanes each add their box's columns at pitch 3, divide and store one byte.  Exactly 3 * out_w * out_h
  *   bytes of an image are stored.
+ *   Phase 1 (column_sums) also takes a column range [c0, c1), c0 a multiple of four -- only the groups and edge columns that
+ *   touch it are summed, and the stage starts at column c0 --, the lanes that share the work and their stage (Lanes), and rows
+ *   that may be none: pixgrid_kernels.hpp's averaged tile kernel calls it with a segment of a row's boxes and a slice of the
+ *   box's rows.  box_kernel passes the whole width, the whole workgroup and the whole box.
  *
  * Row offsets are 64-bit, sums are 32-bit (an all-white 3840 x 2160 frame averaged to 1 x 1 sums to 2 115 072 000; with n / 2
  * added still below 2^32): no 16-bit partial sums, nothing to flush.  No atomics, no inline assembly, no scratch, and only
@@ -218,7 +222,14 @@ template <int BPP> __global__ void __launch_bounds__(PIX_BLOCK) whole_kernel(con
     }
 }
 
-/* a group's sums to the stage: columns 4 * g .. 4 * g + 3, three words each */
+/* the lanes that share a range of columns and rows, and where their sums go (16-aligned LDS) */
+struct Lanes {
+  uint32_t lane, count; /* count >= 3: the columns behind the last whole group take a lane each */
+  uint32_t *stage;
+};
+__device__ inline Lanes whole_workgroup() { return Lanes{threadIdx.x, kBlock, reinterpret_cast<uint32_t *>(ACHIP_SMEM)}; }
+
+/* a group's sums to the stage: columns 4 * g .. 4 * g + 3 of a stage that starts at group g = 0, three words each */
 __device__ inline void stage_group(uint32_t *stage, uint32_t g, const uint32_t (&acc)[12]) {
   uint4 *slot = reinterpret_cast<uint4 *>(stage) + 3u * g;
   slot[0] = make_uint4(acc[0], acc[1], acc[2], acc[3]);
@@ -226,15 +237,21 @@ __device__ inline void stage_group(uint32_t *stage, uint32_t g, const uint32_t (
   slot[2] = make_uint4(acc[8], acc[9], acc[10], acc[11]);
 }
 
-/* stage[3 * x + c] = the sum over rows [y0, y1) of channel c of the RGB24 value of pixel (x, row), for every column x */
-template <int BPP> __device__ inline void column_sums(const asciichat_pix_source_t &s, uint32_t y0, uint32_t y1) {
-  uint32_t *stage = reinterpret_cast<uint32_t *>(ACHIP_SMEM);
+/* stage[3 * (x - c0) + c] = the sum over rows [y0, y1) of channel c of the RGB24 value of pixel (x, row), for the columns x of
+ * the groups that touch [c0, c1) (c0 a multiple of four, c0 < c1 <= width), shared among the lanes of `l`; rows that are none
+ * stage zeros.  box_kernel passes the whole width, the whole workgroup and the whole box (the overload below); the averaged tile
+ * kernel of pixgrid_kernels.hpp a segment of a row's boxes, and where that leaves lanes idle, a slice of the box's rows per part
+ * of the workgroup. */
+template <int BPP>
+__device__ inline void column_sums(const asciichat_pix_source_t &s, uint32_t y0, uint32_t y1, uint32_t c0, uint32_t c1, const Lanes &l) {
+  uint32_t *stage = l.stage;
   const uint32_t w = (uint32_t)s.width, groups = w / 4u;
+  const uint32_t first = c0 / 4u, end = (c1 + 3u) / 4u, last = end < groups ? end : groups; /* the whole groups that touch [c0, c1) */
   const ACHIP_GLOBAL uint8_t *base = global_of(s.pixels);
   const int64_t stride = s.stride;
   const bool swapped = pix_swapped(s.format) != 0;
   const bool in4 = multiple_of(s.pixels, s.stride, 4u), in16 = multiple_of(s.pixels, s.stride, 16u);
-  for (uint32_t g = threadIdx.x; g < groups; g += kBlock) {
+  for (uint32_t g = first + l.lane; g < last; g += l.count) {
     uint32_t acc[12]; /* in memory order: a blue-first group is turned round once, below */
 #pragma unroll
     for (int k = 0; k < 12; k++)
@@ -272,18 +289,23 @@ template <int BPP> __device__ inline void column_sums(const asciichat_pix_source
         acc[3 * k + 2] = t;
       }
     }
-    stage_group(stage, g, acc);
+    stage_group(stage, g - first, acc);
   }
-  const uint32_t x = 4u * groups + threadIdx.x; /* the columns behind the last whole group, one lane each */
-  if (x < w) {
+  const uint32_t x = 4u * groups + l.lane; /* the columns behind the last whole group that lie below c1, one lane each */
+  if (x < w && x < c1) {
     uint32_t acc[3] = {0u, 0u, 0u};
     for (uint32_t r = y0; r < y1; r++) {
       const ACHIP_GLOBAL uint8_t *p = base + pix_at(stride, BPP, (int32_t)x, (int32_t)r);
       const uint32_t v = pix_bytes_rgb(p[0], p[1], p[2], swapped);
       acc[0] += v & 0xFFu, acc[1] += (v >> 8) & 0xFFu, acc[2] += v >> 16;
     }
-    stage[3u * x] = acc[0], stage[3u * x + 1u] = acc[1], stage[3u * x + 2u] = acc[2];
+    stage[3u * (x - c0)] = acc[0], stage[3u * (x - c0) + 1u] = acc[1], stage[3u * (x - c0) + 2u] = acc[2]; /* (c0 <= 4 * groups) */
   }
+}
+
+/* every column of the source, by the whole workgroup: stage[3 * x + c] */
+template <int BPP> __device__ inline void column_sums(const asciichat_pix_source_t &s, uint32_t y0, uint32_t y1) {
+  column_sums<BPP>(s, y0, y1, 0u, (uint32_t)s.width, whole_workgroup());
 }
 
 /* workgroup b: image b / rows_per_image, stored row b % rows_per_image (rows beyond the image's out_h: nothing to do) */

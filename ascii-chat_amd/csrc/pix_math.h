@@ -115,7 +115,7 @@ static inline const char *pix_set_check(const asciichat_pix_source_t *sources, c
     if (f->comp) {
       if (unsupported)
         *unsupported = 1;
-      return "a composite descriptor (its packed tiles go through run_whole first)";
+      return "a composite descriptor (its packed tiles go through asciichat_pixgrid_*, a library of its own)";
     }
     if (f->src_w != sources[i].width || f->src_h != sources[i].height)
       return "src_w x src_h of the descriptor is not the source's size";

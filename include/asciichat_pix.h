@@ -1,7 +1,7 @@
 /*
  * asciichat_pix.h -- libasciichat_pix.so: packed RGB camera frames as they arrive -- RGB24, RGBA, BGR24, BGRA -- in front of the
  * renderers, on the device: only the pixels a render target samples (run), whole frames (run_whole, convert), or the box
- * average straight from the source (run_box, downscale).  A library of its own: it links none of the other six and shares only
+ * average straight from the source (run_box, downscale).  A library of its own: it links none of the other seven and shares only
  * achip_types.h and the error-code values with them.
  *
  * THE RULE (stated here once).  A source is one plane of width x height pixels, both 1..8192.
@@ -32,8 +32,9 @@
  * tight RGBA (lib/video/webcam/wasm/webcam_wasm.c:166-176).  RGB is there so that a server tick with clients of every platform
  * is one set and one launch; for RGB sources the three passes are a gather, a strided copy and the box pass's own arithmetic.
  *
- * Out of scope: the packed tiles of a grid composite (run_whole into the composite's source slots serves them), 16-bit and
- * planar RGB, alpha of any meaning, bottom-up images other than through the descriptor's flip_y.
+ * The packed tiles of a grid composite are libasciichat_pixgrid.so's (include/asciichat_pixgrid.h), sampled or averaged straight
+ * from these sources.  Out of scope: 16-bit and planar RGB, alpha of any meaning, bottom-up images other than through the
+ * descriptor's flip_y.
  *
  * Every call returns 0 or an ASCIICHAT_PIX_ERR_* code and records a message for asciichat_pix_last_error() (per thread).
  * All pointers named *_dev, and the pixels of a source, are device-visible.  A handle's calls belong to one stream.
@@ -87,7 +88,7 @@ int asciichat_pix_create(asciichat_pix_t **h, int max_frames);
 
 /* The tick's sources and, with them, the descriptors achip_frame_setup() made for them (n of each, 1 <= n <= max_frames).
  * Each source is checked against THE RULE, in the order of its sentences.  Of frames[i], src and src_stride are not read; a
- * descriptor with comp is refused with ERR_NOT_SUPPORTED (the packed tiles of a composite go through run_whole first); src_w x
+ * descriptor with comp is refused with ERR_NOT_SUPPORTED (the packed tiles of a composite go through asciichat_pixgrid.h); src_w x
  * src_h must equal source i's size; out_w and out_h are at least 1 and the image below 2^31 bytes; achip_frame_ratios_ok's rule
  * must hold.  frames may be NULL: the handle then serves run_whole only, and run / run_box / render_frames refuse.
  * Checked on the host before anything changes: a refused call leaves the handle as it was.  Sources and descriptors travel in
